@@ -1,7 +1,18 @@
 """Benchmark: the D2D-PPO env-step hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N)
+
+A plain run does what the headline figure needs and nothing else: it sets up the workload below, runs W
+warm-up steps, times K steps, writes the last timed step's outputs when --dump-outputs is given and prints
+one JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step = milliseconds per timed step, ...).
+Everything else described here -- the fp32-obs and in-loop-sampling repeats of the K steps, the legs, the CPU
+baselines -- runs with --full only (and --legs selects among the legs there).
+
+--dump-outputs DIR: what a caller of the last timed step receives (EnvBatch.step's result), as float32 .npy
+files: DIR/reward.npy [E] (every env of rank 0) and DIR/obs.npy [n][N][F], the decoded observation rows of a
+fixed sample of n envs (seeded choice, sorted; all envs when they fit in 32 MiB).  The env seeds, the Philox
+counters and the synthetic actions depend on the arguments alone, so equal arguments give equal files.
 
 Workload (BASELINE.json configs[2]): combinatorial_env, 64 agents x 8 channels,
 channel_switch_8 tiled to 64 rows, deadlines [7,14]x32, heterogeneous traffic
@@ -16,7 +27,7 @@ rows (the reference-API layout, 120 B per agent-step) are reported as `fp32_obs`
 Every episode_length slots the envs reset (inside the timed loop).  Inputs are
 HBM-resident before timing starts.
 
-More legs are reported in the same JSON line (they do not change `value`):
+With --full more legs are reported in the same JSON line (they do not change `value`):
   rollout : the iPPO behaviour-policy slot at the same 65,536 envs — agent-stacked
             actor + critic forward (H=64), Bernoulli sampling, log-probs, action
             packing and the env kernel (ippo.py:293-330 batched);
@@ -1000,6 +1011,27 @@ def gru_c5_leg(args, rank, world, local):
             "sweep": sweep}
 
 
+DUMP_OBS_BYTES = 32 << 20  # obs sample of --dump-outputs (the whole dump stays far below 64 MB)
+
+
+def dump_outputs(dirpath, res, spec, n_envs):
+    """--dump-outputs: the result of the last timed EnvBatch.step (what its caller receives) as float32 .npy
+    files.  reward [E] whole; obs [n][N][F] decoded from the record (or the fp32 rows) for a fixed sample of
+    envs: all of them when they fit DUMP_OBS_BYTES, else a seeded choice without replacement, sorted."""
+    from d2dhip.record import ObsRecord
+    os.makedirs(dirpath, exist_ok=True)
+    n = min(n_envs, max(1, DUMP_OBS_BYTES // (spec.N * spec.F * 4)))
+    idx = np.arange(n_envs) if n == n_envs else np.sort(np.random.default_rng(0).choice(n_envs, n, replace=False))
+    obs = res["obs"]
+    idx_t = torch.from_numpy(idx).to(obs.device)
+    if isinstance(obs, ObsRecord):
+        rows = ObsRecord(obs.data[idx_t].contiguous(), obs.obs_dim, obs.signed).decode()
+    else:
+        rows = obs[idx_t]
+    np.save(os.path.join(dirpath, "obs.npy"), rows.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(dirpath, "reward.npy"), res["reward"].cpu().numpy().astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1009,7 +1041,13 @@ def main():
     ap.add_argument("--episode-length", type=int, default=200)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=8.0)
-    ap.add_argument("--legs", default="env,rollout,ppo,train,configs,d2denv,gru,gru_c5")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline steps: the fp32-obs and in-loop-sampling repeats, "
+                         "the legs (--legs) and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float32)")
+    ap.add_argument("--legs", default=None,
+                    help="with --full: the legs to run (default env,rollout,ppo,train,configs,d2denv,gru,gru_c5)")
     ap.add_argument("--gru-c5-envs", type=int, default=512,
                     help="envs per GPU of the c5 GRU leg (512 x 256 agents = 131,072 GRU windows per slot fill the "
                          "chip; the O(L H^2) BPTT at L = 256 makes a 4,096-env epoch minutes long)")
@@ -1025,6 +1063,12 @@ def main():
     ap.add_argument("--env-mode", default="both", choices=["both", "record", "fp32"],
                     help="obs output of the headline env steps (value = the first of record, fp32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.legs is not None and not args.full:
+        ap.error("--legs selects among the legs of a --full run: add --full")
+    if args.legs is None:
+        args.legs = "env,rollout,ppo,train,configs,d2denv,gru,gru_c5"
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher: start the ranks here, before anything touches the GPU
         sys.exit(self_launch(args.gpus))
@@ -1032,7 +1076,7 @@ def main():
     params = config3_params(args.episode_length)
     world0 = int(os.environ.get("WORLD_SIZE", "1"))
     cpu = None
-    if not args.no_cpu_baseline and world0 == 1:
+    if args.full and not args.no_cpu_baseline and world0 == 1:
         # before any GPU call: the NumPy leg forks one worker per host core
         cpu = cpu_baseline_numpy(params, seconds=args.cpu_seconds)
         cpu["c_openmp"] = cpu_baseline_c(params, seconds=args.cpu_seconds)
@@ -1075,10 +1119,11 @@ def main():
                 step_i[0] += 1
             if ev is not None:
                 ev[0].record()
-            b.step(a_t, want_obs=True, out_obs=out)
+            last[0] = b.step(a_t, want_obs=True, out_obs=out)
             if ev is not None:
                 ev[1].record()
 
+        last = [None]  # the last step's result (--dump-outputs)
         b.reset(want_obs=True, out_obs=out)
         for _ in range(args.warmup):
             one_step()
@@ -1114,24 +1159,28 @@ def main():
                 "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": src,
                 "kernel": env_kernel_name(b.spec, mode == "record"), "kernel_avg_us": kern_avg_ms * 1e3,
                 "bytes_per_launch": bytes_per_launch, "bytes_per_agent_step": bpas}
-        return total_envs * K / t, t, roof
+        return total_envs * K / t, t, roof, last[0]
 
     total_envs = E * world
     modes = ["record", "fp32"] if args.env_mode == "both" else [args.env_mode]
-    env_res = {m: env_phase(m) for m in modes}
-    env_steps_per_s, t, roofline = env_res[modes[0]]
-    vi, ti, _ = env_phase(modes[0], inloop=True)
-    inloop = {"env_steps_per_s": vi, "ms_per_step": ti / K * 1e3,
-              "what": "the same K steps with the synthetic actions sampled on the device inside the timed loop "
-                      "(sample_actions_kernel + env kernel per step; the rounds 1-2 `value` definition)"}
-    fp32_obs = None
-    if len(modes) > 1:
-        v32, t32, r32 = env_res["fp32"]
-        fp32_obs = {"env_steps_per_s": v32, "agent_steps_per_s": v32 * N, "ms_per_step": t32 / K * 1e3,
-                    "roofline": r32,
-                    "what": "the same K steps emitting fp32 obs rows [E][N][F] (the reference-API layout)"}
+    # the headline: the K timed steps in the first mode; its last step's outputs are written before any later
+    # phase reuses the env's output buffers
+    env_steps_per_s, t, roofline, last_res = env_phase(modes[0])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_res, b.spec, E)
+    inloop = fp32_obs = None
+    if args.full:
+        if len(modes) > 1:
+            v32, t32, r32, _ = env_phase("fp32")
+            fp32_obs = {"env_steps_per_s": v32, "agent_steps_per_s": v32 * N, "ms_per_step": t32 / K * 1e3,
+                        "roofline": r32,
+                        "what": "the same K steps emitting fp32 obs rows [E][N][F] (the reference-API layout)"}
+        vi, ti, _, _ = env_phase(modes[0], inloop=True)
+        inloop = {"env_steps_per_s": vi, "ms_per_step": ti / K * 1e3,
+                  "what": "the same K steps with the synthetic actions sampled on the device inside the timed loop "
+                          "(sample_actions_kernel + env kernel per step; the rounds 1-2 `value` definition)"}
 
-    legs = set(args.legs.split(","))
+    legs = set(args.legs.split(",")) if args.full else set()
     rollout = ppo = None
     if "rollout" in legs:
         rollout = rollout_leg(env, args, world)
@@ -1153,6 +1202,7 @@ def main():
             "dist_backend": dist.get_backend() if world > 1 else None,
             "steps": K,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": t / K * 1e3,
             "higher_is_better": True,
             "scaling": "weak",
@@ -1174,7 +1224,8 @@ def main():
             "agent_steps_per_s": env_steps_per_s * N,
             "roofline": roofline,
         }
-        res["with_inloop_action_sampling"] = inloop
+        if inloop is not None:
+            res["with_inloop_action_sampling"] = inloop
         if fp32_obs is not None:
             res["fp32_obs"] = fp32_obs
         if rollout is not None:

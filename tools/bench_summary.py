@@ -1,4 +1,5 @@
-"""Print the headline and the main legs of a bench.py JSON line (file with the line among other output).
+"""Print the headline and the main legs of a `bench.py --full` JSON line (file with the line among other output;
+a plain run's line has no legs).
 usage: python tools/bench_summary.py BENCH.json"""
 import json
 import sys

@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp
 OUT="$R/gpurun_out/pmc_$TAG"; mkdir -p "$OUT"
 run() {
   timeout -k 10 300 rocprofv3 --pmc $2 --kernel-include-regex "$RX" -d "$OUT/$1" -o run --output-format csv -- \
-    python3 "$R/bench.py" --no-cpu-baseline "${BENCH_ARGS[@]}" > "$OUT/$1.log" 2>&1
+    python3 "$R/bench.py" --full --no-cpu-baseline "${BENCH_ARGS[@]}" > "$OUT/$1.log" 2>&1
 }
 BENCH_ARGS=("$@")
 run p1 "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_ACTIVE_INST_VALU" && \

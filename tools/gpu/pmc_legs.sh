@@ -12,7 +12,7 @@ for leg in $LEGS; do
     gru_slot) RX='gru_policy_kernel'; BARGS=(--legs gru --gru-slot-only) ;;
     gru) RX='gru_grad_kernel'; BARGS=(--legs gru) ;;
   esac
-  BARGS+=(--steps 5 --warmup 2 --no-cpu-baseline)
+  BARGS+=(--full --steps 5 --warmup 2 --no-cpu-baseline)
   D="$OUT/$leg"; mkdir -p "$D"
   timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$D/stats" -o run --output-format csv -- \
     python3 "$R/bench.py" "${BARGS[@]}" > "$D/stats.log" 2>&1 || exit 11

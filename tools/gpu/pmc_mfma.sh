@@ -6,7 +6,7 @@ R="$GRAFT_REPO_ROOT"; TAG="$1"; COMMIT="$2"; LEGS="${3:-rollout,ppo,gru}"
 cd /tmp && export TMPDIR=/tmp
 OUT="$R/gpurun_out/pmcm_$TAG"; mkdir -p "$OUT"
 RX='ppo_actor_grad|ppo_critic_grad|policy_split|gru_policy|gru_grad_kernel|gae_scan|normalize_pair|comb_kernel'
-BARGS=(--legs "$LEGS" --steps 20 --warmup 5 --no-cpu-baseline --rollout-steps 20 --ppo-epochs 3)
+BARGS=(--full --legs "$LEGS" --steps 20 --warmup 5 --no-cpu-baseline --rollout-steps 20 --ppo-epochs 3)
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/stats" -o run --output-format csv -- \
   python3 "$R/bench.py" "${BARGS[@]}" > "$OUT/stats.log" 2>&1 || exit 11
 timeout -k 10 400 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAVES GRBM_GUI_ACTIVE \

@@ -4,7 +4,7 @@
 R="$GRAFT_REPO_ROOT"; TAG="${1:-copies}"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --hip-trace --memory-copy-trace --stats -d "$R/gpurun_out/profcp_$TAG" \
-  -o run --output-format csv -- python3 "$R/bench.py" --legs ppo --steps 3 --warmup 1 --ppo-epochs 3 \
+  -o run --output-format csv -- python3 "$R/bench.py" --full --legs ppo --steps 3 --warmup 1 --ppo-epochs 3 \
   --no-cpu-baseline > "$R/gpurun_out/profcp_$TAG.log" 2>&1
 rc=$?; echo "rc=$rc"
 python3 - "$R/gpurun_out/profcp_$TAG" <<'PY'

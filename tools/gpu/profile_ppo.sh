@@ -1,10 +1,11 @@
 # Kernel mix of the PPO-update leg.  usage: bash tools/gpu/profile_ppo.sh <tag>
 R="$GRAFT_REPO_ROOT"; TAG="${1:-ppo}"
+O="${D2D_PROF_OUT:-$R/prof_out}"; mkdir -p "$O"  # where the profiles and logs go
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$R/gpurun_out/profppo_$TAG" -o run --output-format csv -- \
-  python3 "$R/bench.py" --legs ppo --steps 3 --warmup 1 --ppo-epochs 3 --no-cpu-baseline > "$R/gpurun_out/profppo_$TAG.log" 2>&1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$O/profppo_$TAG" -o run --output-format csv -- \
+  python3 "$R/bench.py" --full --legs ppo --steps 3 --warmup 1 --ppo-epochs 3 --no-cpu-baseline > "$O/profppo_$TAG.log" 2>&1
 echo "rc=$?"
-python3 - "$R/gpurun_out/profppo_$TAG/run_kernel_stats.csv" <<'PY'
+python3 - "$O/profppo_$TAG/run_kernel_stats.csv" <<'PY'
 import csv, sys
 rows = list(csv.DictReader(open(sys.argv[1])))
 tot = sum(float(r['TotalDurationNs']) for r in rows)

@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 O="$R/gpurun_out/prof_$TAG"; mkdir -p "$O"
 for mode in fp32 record; do
   if [ "$mode" = fp32 ]; then ALG=567541760; OUT=pmc_traffic_single.json; else ALG=282329088; OUT=pmc_traffic_single_record.json; fi
-  BARGS=(--legs d2denv --d2denv-env-only --steps 5 --warmup 2 --no-cpu-baseline --env-mode $mode)
+  BARGS=(--full --legs d2denv --d2denv-env-only --steps 5 --warmup 2 --no-cpu-baseline --env-mode $mode)
   D="$O/$mode"; mkdir -p "$D"
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$D/stats" -o run --output-format csv -- \
     python3 "$R/bench.py" "${BARGS[@]}" > "$D/stats.log" 2>&1 || exit 11

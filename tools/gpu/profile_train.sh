@@ -1,10 +1,11 @@
 # Kernel mix of the full-scale train leg.  usage: bash tools/gpu/profile_train.sh <tag>
 R="$GRAFT_REPO_ROOT"; TAG="${1:-train}"
+O="${D2D_PROF_OUT:-$R/prof_out}"; mkdir -p "$O"  # where the profiles and logs go
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$R/gpurun_out/proftrain_$TAG" -o run --output-format csv -- \
-  python3 "$R/bench.py" --legs train --steps 2 --warmup 1 --no-cpu-baseline > "$R/gpurun_out/proftrain_$TAG.log" 2>&1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$O/proftrain_$TAG" -o run --output-format csv -- \
+  python3 "$R/bench.py" --full --legs train --steps 2 --warmup 1 --no-cpu-baseline > "$O/proftrain_$TAG.log" 2>&1
 echo "rc=$?"
-python3 - "$R/gpurun_out/proftrain_$TAG/run_kernel_stats.csv" <<'PY'
+python3 - "$O/proftrain_$TAG/run_kernel_stats.csv" <<'PY'
 import csv, sys
 rows = list(csv.DictReader(open(sys.argv[1])))
 tot = sum(float(r['TotalDurationNs']) for r in rows)

@@ -5,7 +5,8 @@ mkdir -p gpurun_out
 timeout -k 10 1000 python -m pytest tests -m gpu -q -p no:cacheprovider > gpurun_out/pytest_gpu.log 2>&1
 rc=$?; echo "pytest rc=$rc"; grep -E "passed|failed" gpurun_out/pytest_gpu.log | tail -2
 [ $rc -le 1 ] || exit $rc
-timeout -k 10 600 python bench.py > gpurun_out/bench_$TAG.log 2>&1
-brc=$?; echo "bench rc=$brc"; tail -c 3000 gpurun_out/bench_$TAG.log
+BLOG="${D2D_PROF_OUT:-$R/prof_out}/bench_$TAG.log"; mkdir -p "$(dirname "$BLOG")"
+timeout -k 10 600 python bench.py --full > "$BLOG" 2>&1
+brc=$?; echo "bench rc=$brc"; tail -c 3000 "$BLOG"
 [ $brc -eq 0 ] || exit $brc
 bash tools/gpu/profile.sh "$TAG"; echo "profile rc=$?"
