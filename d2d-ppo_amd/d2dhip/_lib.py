@@ -94,6 +94,18 @@ class GruDesc(ctypes.Structure):
                 ("obs_format", ctypes.c_int32), ("reserved", ctypes.c_int32), ("obs_signed", _p)]
 
 
+class RdqnDesc(ctypes.Structure):
+    _fields_ = [("n_agents", ctypes.c_int32), ("n_envs", ctypes.c_int32), ("obs_dim", ctypes.c_int32),
+                ("hidden", ctypes.c_int32), ("n_out", ctypes.c_int32), ("ring_rows", ctypes.c_int32),
+                ("ring_episode", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("w_ih", _p), ("w_hh", _p), ("b_ih", _p), ("b_hh", _p), ("w1", _p), ("b1", _p), ("w2", _p), ("b2", _p),
+                ("w3", _p), ("b3", _p), ("seed", ctypes.c_uint64), ("env_base", ctypes.c_uint64), ("rng_offset", _p)]
+
+
+D2D_RDQN_GREEDY, D2D_RDQN_EPS, D2D_RDQN_FORCED = 0, 1, 2
+D2D_RDQN_HUBER, D2D_RDQN_MSE = 0, 1
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "d2d_env_reset": (ctypes.c_int, [ctypes.POINTER(EnvDesc), ctypes.POINTER(EnvState), ctypes.POINTER(EnvReplay),
@@ -163,6 +175,11 @@ _SIGS = {
     "d2d_gru_grad": (ctypes.c_int, [ctypes.POINTER(GruDesc), ctypes.c_int32, _p, _p, _p, _p, _p, _p, ctypes.c_float,
                                      ctypes.c_float, ctypes.c_float, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
                                      ctypes.c_int64, _p]),
+    "d2d_rdqn_q": (ctypes.c_int, [ctypes.POINTER(RdqnDesc), _p, _p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                   ctypes.c_float, _p, ctypes.c_int32, _p, _p, ctypes.c_uint32, _p, _p, _p, _p]),
+    "d2d_rdqn_grad_workspace": (ctypes.c_int64, [ctypes.POINTER(RdqnDesc), ctypes.c_int32, ctypes.c_int32]),
+    "d2d_rdqn_grad": (ctypes.c_int, [ctypes.POINTER(RdqnDesc), _p, _p, ctypes.c_int32, ctypes.c_int32, _p, _p, _p, _p,
+                                      ctypes.c_float, ctypes.c_int32] + [_p] * 12 + [ctypes.c_int64, _p]),
     "d2d_last_error": (ctypes.c_char_p, []),
     "d2d_abi_version": (ctypes.c_int, []),
 }

@@ -51,7 +51,8 @@ extern "C" {
                               11: D2D_OPT_CRITIC_GRAD_ROWS; 12: d2d_ppo_critic_grad_values, d2d_central_critic_*;
                               13: d2d_comb_policy_fused_step, D2D_OPT_FUSED_SLICE, d2d_env_out.state_bf16;
                               14: d2d_policy_gru_carry, d2d_gru_carry_floats, d2d_central_critic_dw1, single obs_record;
-                              15: actions = NULL in forced mode (d2d_policy_mlp_step, d2d_policy_gru) */
+                              15: actions = NULL in forced mode (d2d_policy_mlp_step, d2d_policy_gru);
+                              still 15, additive: d2d_rdqn_q, d2d_rdqn_grad, d2d_rdqn_grad_workspace (iRDQN) */
 
 enum { D2D_ENV_COMBINATORIAL = 0, D2D_ENV_CHANNEL_SELECTION = 1, D2D_ENV_SINGLE = 2 };
 enum { D2D_ARRIVAL_POISSON = 0, D2D_ARRIVAL_SCHEDULED_BERNOULLI = 1, D2D_ARRIVAL_NONE = 2 };
@@ -460,6 +461,59 @@ int d2d_gru_grad(const d2d_gru_desc* desc, int32_t T, const void* obs, const voi
                  float beta, float scale, float* g_w_ih, float* g_w_hh, float* g_b_ih, float* g_b_hh, float* g_w1,
                  float* g_b1, float* g_w2, float* g_b2, float* stats, float* workspace, int64_t workspace_floats,
                  void* stream);
+
+/* ---- iRDQN: recurrent DQN for every agent at once (the reference's algorithms/irdqn.py) ----
+ * Per agent the RNN module of irdqn.py:58-86: torch.nn.GRU(F, H) (w_ih [N][3H][F], w_hh [N][3H][H], b_ih, b_hh
+ * [N][3H], gate order r, z, n) -> Linear(H, H) w1, b1 -> ReLU -> Linear(H, H) w2, b2 -> ReLU -> Linear(H, A) w3
+ * [N][A][H], b3 [N][A], no output activation; agent-stacked fp32, h0 = 0 for every window.
+ * Observations come from an fp32 ring obs [ring_rows][n_envs][N][F].  A window is given per sample b by the device
+ * triple samples[b] = (env, last, length): with ring_episode == 0 its rows are last - length + 1 .. last of that env
+ * (modulo ring_rows), unpadded (the acting window, irdqn.py:242-265).  With ring_episode = T > 0 the ring holds whole
+ * episodes of T + 1 rows (the reset obs and every next obs) and the indices are TRANSITIONS of the env's timeline
+ * (modulo the ring's ring_rows / (T + 1) * T transitions): transition m reads row m + m / T + row_shift, row_shift 0 for
+ * its state and 1 for its successor state, so a training chunk may straddle an episode boundary (irdqn.py:24-42)
+ * and s' is not stored twice.
+ * Envelope: hidden <= 128, obs_dim + 1 <= 64, n_out <= 16, window length <= 256, any batch; else
+ * D2D_EUNSUPPORTED before any launch.  Products are exact fp32 (v_mfma_f32_16x16x4_f32), fp32 accumulation. */
+typedef struct d2d_rdqn_desc {
+    int32_t n_agents, n_envs, obs_dim, hidden, n_out;
+    int32_t ring_rows, ring_episode, reserved;
+    const float *w_ih, *w_hh, *b_ih, *b_hh, *w1, *b1, *w2, *b2, *w3, *b3;
+    uint64_t seed, env_base;
+    const uint32_t* rng_offset;  /* optional device uint32 added to rng_step, as in d2d_gru_desc */
+} d2d_rdqn_desc;
+
+enum { D2D_RDQN_GREEDY = 0, D2D_RDQN_EPS = 1, D2D_RDQN_FORCED = 2 };
+enum { D2D_RDQN_HUBER = 0, D2D_RDQN_MSE = 1 };
+
+/* Q-values of B windows for every agent in one launch (DQN.act, irdqn.py:150-160; the target's max of
+ * DQN.train_step, irdqn.py:139-141).  Outputs, each optional (NULL): q [N][B][A], qmax [N][B], action [B][N] as the
+ * one-hot channel mask of the env kernels' action format (d2d_mask_bytes(n_out) bytes, bit c = action c).
+ * mode D2D_RDQN_GREEDY: the argmax, lowest index on ties.  D2D_RDQN_EPS: one Philox uniform u (stream 4) per
+ * (env_base + env, agent, rng_step); greedy if ready && u >= eps, else an explore action drawn from {0, 1} -- the
+ * reference's np.random.randint(0, 2), irdqn.py:154, whatever n_out is; eps_rows != NULL gives every sample its own
+ * epsilon [B] instead of eps (envs of one batch at different episodes; a value above 1 always explores).  D2D_RDQN_FORCED: explore_mask [B][N] != 0
+ * replaces the greedy action by explore_action [B][N] (uint8 each). */
+int d2d_rdqn_q(const d2d_rdqn_desc* desc, const float* obs, const int32_t* samples, int32_t B, int32_t row_shift,
+               int32_t mode, float eps, const float* eps_rows, int32_t ready, const uint8_t* explore_mask,
+               const uint8_t* explore_action,
+               uint32_t rng_step, float* q, float* qmax, void* action, void* stream);
+
+/* One TD update's gradients for every agent (DQN.train_step, irdqn.py:133-148, on the chunks iRDQN.train builds,
+ * irdqn.py:292-297): per sample b the window of exactly L transitions ending at samples[b].last (the length field is
+ * ignored; row_shift 0), action [B][N] (one-hot masks as above), reward [B][N], done [B] (uint8) of the window's last
+ * transition and qmax_target [N][B] (d2d_rdqn_q of the target parameters on the same samples with row_shift 1):
+ *   td = r + (1 - done) gamma qmax_target,  delta = Q[action] - td,
+ *   loss = mean_b smooth_l1(delta) (D2D_RDQN_HUBER, beta = 1) or mean_b delta^2 (D2D_RDQN_MSE),
+ * backward through the head and the L GRU steps.  Outputs (overwritten): the ten gradients in the parameters' shapes
+ * and loss [N].  Sums run in a fixed order without atomics: bitwise reproducible.  workspace:
+ * d2d_rdqn_grad_workspace(desc, B, L) floats of device scratch (16-byte aligned; x, h and gate history). */
+int64_t d2d_rdqn_grad_workspace(const d2d_rdqn_desc* desc, int32_t B, int32_t L);
+int d2d_rdqn_grad(const d2d_rdqn_desc* desc, const float* obs, const int32_t* samples, int32_t B, int32_t L,
+                  const void* action, const float* reward, const uint8_t* done, const float* qmax_target, float gamma,
+                  int32_t loss_kind, float* g_w_ih, float* g_w_hh, float* g_b_ih, float* g_b_hh, float* g_w1,
+                  float* g_b1, float* g_w2, float* g_b2, float* g_w3, float* g_b3, float* loss, float* workspace,
+                  int64_t workspace_floats, void* stream);
 
 /* Process-wide tuning options (not part of the reference interface).
  * D2D_OPT_NT_STORES: 1 = write obs/state with non-temporal (streaming) stores.
