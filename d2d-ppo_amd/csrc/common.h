@@ -28,18 +28,11 @@ __device__ __forceinline__ u32x4 philox(uint32_t c0, uint32_t c1, uint32_t c2, u
     // one 32x32->64 multiply per product (v_mad_u64_u32) gives both halves
     const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
     const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
-#ifndef D2D_PHILOX_XOR3
-#define D2D_PHILOX_XOR3 1
-#endif
-#if D2D_PHILOX_XOR3
     // three-input xor in one v_bitop3_b32 (the compiler emits two v_xor_b32; the key words are
     // kernel-argument uniform, hence SGPR operands): comb step 65.4 -> 62.7 us at 64 x 8 x 65,536
     uint32_t n0, n2;
     asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x96" : "=v"(n0) : "v"((uint32_t)(p1 >> 32)), "v"(c1), "s"(k0));
     asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x96" : "=v"(n2) : "v"((uint32_t)(p0 >> 32)), "v"(c3), "s"(k1));
-#else
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-#endif
     c0 = n0;
     c1 = (uint32_t)p1;
     c2 = n2;

@@ -77,38 +77,22 @@ __device__ __forceinline__ bf16x8 cat_tr16(v4i16 a, v4i16 b) {
 }
 __device__ __forceinline__ float bf_hi(uint32_t p) { return __uint_as_float(p & 0xFFFF0000u); }
 
-#ifndef D2D_CRITIC_WAVES
-// waves per workgroup (2 per SIMD either way): 8 halves the W1 image slices each sample's workgroup reads from L2
+// waves per workgroup (2 per SIMD either way): 8 would halve the W1 image slices each sample's workgroup reads from L2
 // and writes to LDS
-#define D2D_CRITIC_WAVES 4
-#endif
-#ifndef D2D_CRITIC_XLDS
-// 1: the operand through LDS in full 128-byte lines (KCH = 2, ST = 4): each load instruction brings 8 sample rows x 128 B
-// (the iteration's two chunks) instead of 16 rows x 64 B, the rows are written to a per-wave XOR-swizzled image and the
-// MFMA B fragments read back by ds_read_b128 (MI355X_MICROARCH / cdna_hip_programming: fragment-shaped loads cost the
-// texture path twice the work of full-line ones)
-#define D2D_CRITIC_XLDS 1
-#endif
-#ifndef D2D_CRITIC_WPD
-// XL path: W1's image slices loaded 1 iteration ahead, or (2) two ahead in two register sets -- measured 4 % SLOWER
-// (1.82-1.84 vs 1.75-1.76 ms per epoch at 256 agents, profiles/r05/critic_wpd: +46 VGPRs, and the slice is L2-resident)
-#define D2D_CRITIC_WPD 1
-#endif
-#ifndef D2D_CRITIC_PD
-// operand prefetch distance in iterations + 1: 3 = three register sets in rotation (two iterations in flight), 2 =
-// two sets, the next iteration's chunks only (round 5 first version)
-#define D2D_CRITIC_PD 3
-#endif
+constexpr int kCriticWaves = 4;
 // KCH chunks of 32 features per iteration (one barrier per iteration; the operand loads of the next iteration in
 // flight behind this one's 48 KCH MFMAs per wave: at KCH = 1 the kernel read the 6.3 GB operand at ~3 TB/s)
 template <int HT, int ST, int KCH>
-__global__ __launch_bounds__(64 * D2D_CRITIC_WAVES, 8 / D2D_CRITIC_WAVES) void critic_fwd_kernel(CriticArgs a) {
-  constexpr int WV = D2D_CRITIC_WAVES, NT = 64 * WV;  // waves / threads per workgroup
+__global__ __launch_bounds__(64 * kCriticWaves, 8 / kCriticWaves) void critic_fwd_kernel(CriticArgs a) {
+  constexpr int WV = kCriticWaves, NT = 64 * WV;  // waves / threads per workgroup
   constexpr int NI = HT * 3 * 64;  // 16-byte image entries per chunk
-  // XL: the operand through the per-wave LDS image (D2D_CRITIC_XLDS): 64 rows x 8 16-byte slots per wave, slot s of row r
+  // XL (KCH = 2, ST = 4): the operand through LDS in full 128-byte lines.  Each load instruction brings 8 sample rows
+  // x 128 B (the iteration's two chunks) instead of 16 rows x 64 B (fragment-shaped loads cost the texture path twice
+  // the work of full-line ones); the rows are written to a per-wave image and the MFMA B fragments read back by
+  // ds_read_b128.  The image: 64 rows x 8 16-byte slots per wave, slot s of row r
   // at r * 8 + (s ^ ((r >> 1) & 7)) -- conflict-free for the 8-lane row writes and the 16-lane groups of the fragment
   // reads; the workgroup's sums reuse wave 0's image after the loop (80 KB per workgroup: two per CU)
-  constexpr bool XL = D2D_CRITIC_XLDS && KCH == 2 && ST == 4;
+  constexpr bool XL = KCH == 2 && ST == 4;
   constexpr int NRED = WV * (2 * 16 * HT + 2);
   __shared__ __attribute__((aligned(16))) bf16x8 wl[2][KCH * NI];
   __shared__ __attribute__((aligned(16))) uint4 xim[XL ? WV : 1][XL ? 64 * 8 : 1];
@@ -151,8 +135,8 @@ __global__ __launch_bounds__(64 * D2D_CRITIC_WAVES, 8 / D2D_CRITIC_WAVES) void c
     for (int t = 0; t < HT; ++t) acc[st][t] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   const int iters = a.nchunk / KCH;  // (nchunk is padded to a multiple of KCH; the image is zero there)
-  // one iteration: W1's image slice of iteration it to LDS, the next slice's and (PD) the operand chunks of iteration
-  // it + PD - 1 into flight, one barrier, the MFMAs on xc
+  // one iteration: W1's image slice of iteration it to LDS, the next slice's and the operand chunks of iteration
+  // it + 2 into flight, one barrier, the MFMAs on xc
   auto body = [&](int it, const bf16x8 (&xc)[KCH][ST], bf16x8 (&xl)[KCH][ST]) {
     // buffer it & 1 was last read in iteration it - 2: every wave passed iteration it - 1's barrier since
 #pragma unroll
@@ -161,7 +145,7 @@ __global__ __launch_bounds__(64 * D2D_CRITIC_WAVES, 8 / D2D_CRITIC_WAVES) void c
       if (NE % NT == 0 || e < NE) wl[it & 1][e] = wr[q];
     }
     if (it + 1 < iters) load_w(it + 1);
-    if (it + D2D_CRITIC_PD - 1 < iters) load_x(xl, it + D2D_CRITIC_PD - 1);
+    if (it + 2 < iters) load_x(xl, it + 2);
     __syncthreads();
 #pragma unroll
     for (int q = 0; q < KCH; ++q)
@@ -192,9 +176,9 @@ __global__ __launch_bounds__(64 * D2D_CRITIC_WAVES, 8 / D2D_CRITIC_WAVES) void c
       }
     };
     uint4* own = &xim[XL ? wave : 0][0];
-    // W1's image slices two iterations ahead in two register sets (the loop unrolled by two: no set is copied),
-    // the operand one iteration ahead
-    bf16x8 wr2[NW];
+    // W1's image slice and the operand both one iteration ahead (the slice is L2-resident: a second register set
+    // two iterations ahead measured slower).  The register set is passed by reference: written on `wr` directly the
+    // same loop gets another register assignment
     auto load_w2 = [&](bf16x8 (&w)[NW], int it) {
 #pragma unroll
       for (int q = 0; q < NW; ++q) {
@@ -217,7 +201,7 @@ __global__ __launch_bounds__(64 * D2D_CRITIC_WAVES, 8 / D2D_CRITIC_WAVES) void c
         own[r * 8 + ((lane & 7) ^ ((r >> 1) & 7))] = xv[j];
       }
       if (it + 1 < iters) load_xl(it + 1);
-      if (it + D2D_CRITIC_WPD < iters) load_w2(wc, it + D2D_CRITIC_WPD);
+      if (it + 1 < iters) load_w2(wc, it + 1);
       __syncthreads();
 #pragma unroll
       for (int q = 0; q < KCH; ++q) {
@@ -241,18 +225,9 @@ __global__ __launch_bounds__(64 * D2D_CRITIC_WAVES, 8 / D2D_CRITIC_WAVES) void c
       }
     };
     load_xl(0);
-#if D2D_CRITIC_WPD == 2
-    if (iters > 1) load_w2(wr2, 1);
-    for (int it = 0; it < iters; it += 2) {
-      xbody(it, wr);
-      if (it + 1 < iters) xbody(it + 1, wr2);
-    }
-#else
     for (int it = 0; it < iters; ++it) xbody(it, wr);
-#endif
     __syncthreads();  // wave 0's image becomes the workgroup's sums below
   } else {
-#if D2D_CRITIC_PD == 3
   // three operand register sets in rotation (the loop unrolled by three, so no set is copied: a copy would wait on
   // its load at the end of the iteration that issued it): each chunk's loads are in flight for two iterations
   bf16x8 x0[KCH][ST], x1[KCH][ST], x2[KCH][ST];
@@ -263,17 +238,6 @@ __global__ __launch_bounds__(64 * D2D_CRITIC_WAVES, 8 / D2D_CRITIC_WAVES) void c
     if (it + 1 < iters) body(it + 1, x1, x0);
     if (it + 2 < iters) body(it + 2, x2, x1);
   }
-#else
-  bf16x8 xc[KCH][ST], xn[KCH][ST];
-  load_x(xc, 0);
-  for (int it = 0; it < iters; ++it) {
-    body(it, xc, xn);
-#pragma unroll
-    for (int q = 0; q < KCH; ++q)
-#pragma unroll
-      for (int st = 0; st < ST; ++st) xc[q][st] = xn[q][st];
-  }
-#endif
   }
 
   // ---- epilogue: bias, relu, value, dv, dpre's split; the lane's sums over its samples
@@ -547,19 +511,16 @@ __global__ __launch_bounds__(256) void critic_dw1_reduce_kernel(int64_t n, int K
 using namespace d2d;
 
 static int critic_ht(int H) { return H <= 32 ? 2 : H <= 64 ? 4 : H <= 128 ? 8 : 0; }
-#ifndef D2D_CRITIC_ST4
-// sample tiles per wave / chunks per iteration at HT = 3..4 (A/B builds; the XL path needs 4 / 2)
-#define D2D_CRITIC_ST4 4
-#define D2D_CRITIC_KCH4 2
-#endif
-static int critic_st(int ht) { return ht <= 2 ? 4 : ht <= 4 ? D2D_CRITIC_ST4 : 2; }
-static int critic_kch(int ht) { return ht <= 2 ? 2 : ht <= 4 ? D2D_CRITIC_KCH4 : 1; }  // chunks per iteration (LDS: 2 x KCH x 12 HT/4 KB)
+// sample tiles per wave / chunks per iteration at HT = 3..4 (the XL path needs 4 / 2)
+constexpr int kCriticSt4 = 4, kCriticKch4 = 2;
+static int critic_st(int ht) { return ht <= 2 ? 4 : ht <= 4 ? kCriticSt4 : 2; }
+static int critic_kch(int ht) { return ht <= 2 ? 2 : ht <= 4 ? kCriticKch4 : 1; }  // chunks per iteration (LDS: 2 x KCH x 12 HT/4 KB)
 static int critic_chunks(int ht, int S) { const int k = critic_kch(ht); return ((S + 31) / 32 + k - 1) / k * k; }
 
 extern "C" int32_t d2d_central_critic_blocks(int32_t H, int64_t B) {
   const int ht = critic_ht(H);
   if (ht == 0 || B <= 0) return 0;
-  const int64_t per = 16 * D2D_CRITIC_WAVES * critic_st(ht);
+  const int64_t per = 16 * kCriticWaves * critic_st(ht);
   return (int32_t)((B + per - 1) / per);
 }
 
@@ -594,13 +555,13 @@ extern "C" int d2d_central_critic_fwd(int32_t H, int64_t B, int32_t S, int64_t l
   bf16x8* img = reinterpret_cast<bf16x8*>(w1img);
   if (ht == 2) {
     hipLaunchKernelGGL(critic_w1_image_kernel<2>, dim3(ig), dim3(256), 0, s, H, S, a.nchunk, w1, img);
-    hipLaunchKernelGGL((critic_fwd_kernel<2, 4, 2>), dim3(G), dim3(64 * D2D_CRITIC_WAVES), 0, s, a);
+    hipLaunchKernelGGL((critic_fwd_kernel<2, 4, 2>), dim3(G), dim3(64 * kCriticWaves), 0, s, a);
   } else if (ht == 4) {
     hipLaunchKernelGGL(critic_w1_image_kernel<4>, dim3(ig), dim3(256), 0, s, H, S, a.nchunk, w1, img);
-    hipLaunchKernelGGL((critic_fwd_kernel<4, D2D_CRITIC_ST4, D2D_CRITIC_KCH4>), dim3(G), dim3(64 * D2D_CRITIC_WAVES), 0, s, a);
+    hipLaunchKernelGGL((critic_fwd_kernel<4, kCriticSt4, kCriticKch4>), dim3(G), dim3(64 * kCriticWaves), 0, s, a);
   } else {
     hipLaunchKernelGGL(critic_w1_image_kernel<8>, dim3(ig), dim3(256), 0, s, H, S, a.nchunk, w1, img);
-    hipLaunchKernelGGL((critic_fwd_kernel<8, 2, 1>), dim3(G), dim3(64 * D2D_CRITIC_WAVES), 0, s, a);
+    hipLaunchKernelGGL((critic_fwd_kernel<8, 2, 1>), dim3(G), dim3(64 * kCriticWaves), 0, s, a);
   }
   D2D_CHECK_HIP(hipGetLastError());
   return D2D_OK;

@@ -19,7 +19,6 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 
 #include "common.h"
@@ -31,14 +30,9 @@ constexpr int kBlock = 256;
 // comb_kernel register budget and the lane count of a record-only step (no LDS staging): 7 waves
 // per SIMD (<= 72 VGPRs, no spills; unhinted the allocator takes 91 and runs 5) in 256-lane blocks
 // (512-lane blocks would fit only 3 per SIMD pair of waves): record step 68.5 -> 64.9 us at
-// 64 x 8 x 65,536; 8 waves spill (76 us).  Ablation builds override both
-// (tools/gpu/build_ablate_env.sh).
-#ifndef D2D_COMB_WAVES_PER_EU
-#define D2D_COMB_WAVES_PER_EU 7
-#endif
-#ifndef D2D_COMB_REC_BLOCK
-#define D2D_COMB_REC_BLOCK 256
-#endif
+// 64 x 8 x 65,536; 8 waves spill (76 us).
+constexpr int kCombWavesPerEu = 7;
+constexpr int kCombRecBlock = 256;
 constexpr int kMaxAgents = 1024;
 
 struct EnvArgs {
@@ -636,7 +630,7 @@ __device__ __forceinline__ void comb_step(const EnvArgs a, float* lds, int bidx,
 }
 
 template <typename MaskT, int DW, bool LARGE, int CT, bool RESET>
-__global__ __launch_bounds__(kMaxAgents) __attribute__((amdgpu_waves_per_eu(D2D_COMB_WAVES_PER_EU))) void comb_kernel(EnvArgs a) {
+__global__ __launch_bounds__(kMaxAgents) __attribute__((amdgpu_waves_per_eu(kCombWavesPerEu))) void comb_kernel(EnvArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   comb_step<MaskT, DW, LARGE, CT, RESET>(a, lds, blockIdx.x, nullptr, 0, 0);
 }
@@ -1095,20 +1089,10 @@ using namespace d2d;
 
 namespace {
 
-// streaming (non-temporal) stores for the obs/state flush: d2d_set_option(D2D_OPT_NT_STORES, v),
-// initial value from the environment variable D2D_NT_STORES
-// (a relaxed atomic: d2d_set_option may run on another host thread; -1 = not yet read from the environment)
-std::atomic<int> g_nt_stores{-1};
-uint32_t store_flags() {
-  int v = g_nt_stores.load(std::memory_order_relaxed);
-  if (v < 0) {
-    const char* e = getenv("D2D_NT_STORES");
-    int expect = -1;
-    g_nt_stores.compare_exchange_strong(expect, (e && e[0] == '1') ? 1 : 0, std::memory_order_relaxed);
-    v = g_nt_stores.load(std::memory_order_relaxed);
-  }
-  return (uint32_t)v;
-}
+// streaming (non-temporal) stores for the obs/state flush: d2d_set_option(D2D_OPT_NT_STORES, v)
+// (a relaxed atomic: d2d_set_option may run on another host thread)
+std::atomic<int> g_nt_stores{0};
+uint32_t store_flags() { return (uint32_t)g_nt_stores.load(std::memory_order_relaxed); }
 
 int buffer_words(int D) { return D <= 4 ? 1 : D <= 8 ? 2 : D <= 12 ? 3 : D <= 16 ? 4 : 8; }
 
@@ -1299,7 +1283,7 @@ int run_env(const d2d_env_desc* d, const d2d_env_state* st, const void* actions,
   // 512: 125 us, 1024: 134 us per 65,536 x 64-agent step)
   // 512-lane blocks (8 envs of 64 agents): comb 64 x 8 x 65,536 141 -> 137 us against 256-lane
   // blocks; single: 8 envs per gather-table read (256: 130 us, 512: 125 us, 1024: 134 us)
-  int block = large ? a.seg : (comb && !a.obs && !a.state && !a.state_b) ? D2D_COMB_REC_BLOCK : 512;
+  int block = large ? a.seg : (comb && !a.obs && !a.state && !a.state_b) ? kCombRecBlock : 512;
   a.cnt_words = cnt_words(large ? 1 : block / a.seg);
   while (!large && block > kWave && block > a.seg && lds_need(a, block, kind) > 65536) {
     block >>= 1;

@@ -283,9 +283,6 @@ __device__ __forceinline__ void gru_gates(const f32x4 (&rz)[2 * HT], const f32x4
 // the weight images store each A fragment with the same permuted columns: fragment (T, c, part) of
 // lane (g, i) = the 8 k-slots of row 16T + i, as one 16-byte word ([T][c][part][lane], conflict-free
 // ds_read_b128).  Odd tile counts leave the upper half of the last chunk zero on both sides.
-#ifndef D2D_GRU_ABLATE_X
-#define D2D_GRU_ABLATE_X 0  // != 0 only in tools/gpu/build_ablate_gru.sh's variant 7 (timing only)
-#endif
 // bf16 high parts of 8 floats (their exact value when the inputs are bf16-exact)
 __device__ __forceinline__ bf16x8 hi_frag_(const float (&v)[8]) {
   uint32_t u[4];
@@ -402,23 +399,6 @@ __device__ __forceinline__ void chunk_vals(float (&v)[8], const float (&t)[NTL][
   for (int j = 0; j < 8; ++j) v[j] = 2 * c + (j >> 2) < NTL ? t[2 * c + (j >> 2)][j & 3] : 0.f;
 }
 
-// acc += W.X with all split products of weight >= 2^-24 (mfma_split's six plus m.l and l.m; only
-// l.l dropped): ~2^-32 relative per product.  Ablation D2D_GRU_SPLIT8: measured 12 % slower per
-// policy slot than the default six terms (2^-23 per product, the MLP kernels' choice) with the same
-// worst-case log-prob error in tests/test_gru_gpu.py (tools/gpu/gru_diag.py: the window's fp32 gate
-// math and the fp32 Bernoulli probabilities dominate, not the product split).
-__device__ __forceinline__ f32x4 mfma_split8(const Parts& w, const Parts& x, f32x4 acc) {
-  acc = mfma_bf16(w.m, x.l, acc);
-  acc = mfma_bf16(w.l, x.m, acc);
-  acc = mfma_bf16(w.h, x.l, acc);
-  acc = mfma_bf16(w.m, x.m, acc);
-  acc = mfma_bf16(w.l, x.h, acc);
-  acc = mfma_bf16(w.h, x.m, acc);
-  acc = mfma_bf16(w.m, x.h, acc);
-  acc = mfma_bf16(w.h, x.h, acc);
-  return acc;
-}
-
 // gru_preact on the split images.  x_exact (wave-uniform): every input of the step is bf16-exact
 // (always for the compact record), so the input products need only the three weight parts.
 // XEXACT: the inputs are bf16-exact by construction (the compact record) -- no per-tile branch on
@@ -475,7 +455,7 @@ __device__ __forceinline__ void gru_preact_split(const bf16x8* wih_b, const bf16
     for (int T = 0; T < S::NT; ++T) {
       f32x4 a = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int c = 0; c < (D2D_GRU_ABLATE_X ? 0 : S::CI); ++c) {
+      for (int c = 0; c < S::CI; ++c) {
         a = mfma_bf16(wi[T][c][2], xh[c], a);
         a = mfma_bf16(wi[T][c][1], xh[c], a);
         a = mfma_bf16(wi[T][c][0], xh[c], a);
@@ -505,7 +485,7 @@ __device__ __forceinline__ void gru_preact_split(const bf16x8* wih_b, const bf16
   for (int T = 0; T < S::NT; ++T) {
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int c = 0; c < (D2D_GRU_ABLATE_X ? 0 : S::CI); ++c) {  // (timing ablation: no input products)
+    for (int c = 0; c < S::CI; ++c) {
       const bf16x8* wf = wih_b + ((T * S::CI + c) * 3) * 64 + lane;
       acc = mfma_split(Parts{wf[0], wf[64], wf[128]}, xp[c], x_exact, acc);
     }
@@ -529,11 +509,7 @@ __device__ __forceinline__ void gru_preact_split(const bf16x8* wih_b, const bf16
 #pragma unroll
     for (int c = 0; c < S::CH; ++c) {
       const bf16x8* wf = whh_b + ((T * S::CH + c) * 3) * 64 + hl;
-#if D2D_GRU_SPLIT8  // ablation: eight terms
-      acc = mfma_split8(Parts{wf[0], wf[64], wf[128]}, hp[c], acc);
-#else
       acc = mfma_split(Parts{wf[0], wf[64], wf[128]}, hp[c], false, acc);
-#endif
     }
     if (T < 2 * HT) rz[T] = acc;
     else nh[T - 2 * HT] = acc;

@@ -25,36 +25,6 @@
 #include "policy_epilogue.h"
 #include "ppo_epilogue.h"
 
-#ifndef D2D_GRU_ABLATE
-// != 0 only in tools/gpu/build_ablate_gru.sh's timing builds (wrong gradients by design):
-// 1 no weight-gradient GEMMs, 2 no dh MFMAs, 3 no history staging, 4 no BPTT gate recompute
-#define D2D_GRU_ABLATE 0
-#endif
-
-#ifndef D2D_GRU_DW_BF16
-// 1 (default since round 3): the update kernel's weight-gradient GEMMs dW_hh = sum dgh h^T, dW_ih = sum
-// dgi x^T on v_mfma_f32_16x16x32_bf16 over two-way RNE splits of the history operands (~2^-17 relative
-// per product term, as the MLP update kernels' dW1 / dW2; x is bf16-exact): 60 bf16 MFMAs of 16 cycles
-// per step and pass instead of 144 fp32 MFMAs of 32 (298 -> 278 ms per 3.3 M agent-samples,
-// profiles/r03).  Round 2 kept it off because one D2D categorical GRU reference trace missed a flat
-// 1e-4 final-weight bar (1.5e-4 on one of 768 elements, an element whose gradient is ~0, where Adam's
-// normalised step is decided by rounding); the learner parity test now bounds every final weight by
-// Adam's own sensitivity to the gradient error the kernels are held to (tests/test_learner_gpu.py
-// adam bound), and every GRU gradient / learner / driver test passes on it.  0: v_mfma_f32_16x16x4_f32
-// with exact products (fp32 numerics).
-#define D2D_GRU_DW_BF16 1
-#endif
-
-#ifndef D2D_GRU_DH_BF16
-// 1: the BPTT's dh_{j-1} = W_hh^T dg on v_mfma_f32_16x16x32_bf16: the transposed W_hh image holds a
-// two-way RNE bf16 split [W_h(4 rows) | W_m(4 rows)] per (unit, gate tile, lane group) -- 16 bytes, the
-// same LDS as the fp32 image -- and dg is split two ways per step, so one A fragment serves two MFMAs
-// (B = [g_h | g_h] and [g_m | g_m]: W_h g_h + W_m g_h + W_h g_m + W_m g_m, ~2^-16 relative per product).
-// 96 bf16 MFMAs of 16 cycles per step instead of 192 fp32 v_mfma_f32_16x16x4_f32 of 32.
-// 0: the fp32 MFMAs on the fp32 transposed image (exact products).
-#define D2D_GRU_DH_BF16 1
-#endif
-
 namespace d2d {
 
 // RNE bf16 pair (lo = a, hi = b) and the residual pair, as two dwords each (the dh GEMM's B operands)
@@ -435,7 +405,7 @@ __device__ __forceinline__ bf16x8 whh_dh_frag(const bf16x8* whh_b, int T, int t,
 // then 2 HW rows per wave (the step's gradient rows leave it in three passes), 155 KB in all.
 // LONGW (COOP): windows longer than kFlushSteps steps, the cooperative accumulators flushed every kFlushSteps
 //
-// PADC (COOP, D2D_GRU_PAD_COLLAPSE): the BPTT of the front-padding region once per wave instead of once per
+// PADC (= COOP): the BPTT of the front-padding region once per wave instead of once per
 // tile.  A padding step j < pad has the same h_{j-1} (the padding table), the same x (the bias input) and
 // hence the same gates for every sample, so the backward through the padding region is one LINEAR map of
 // dh_{pad-1}, the same for every sample, and so are the weight-gradient rows it produces (dg (x) h_{j-1},
@@ -444,21 +414,20 @@ __device__ __forceinline__ bf16x8 whh_dh_frag(const bf16x8* whh_b, int T, int t,
 // extra all-padding pass after the last round runs j = L-2 .. 0 once with dh += ent[j] at each step.
 // Exact in real arithmetic; in fp32 only the summation order of the padding rows' contributions changes.
 // Saves the padding steps' share of the BPTT: ~16 % at L = 64 (ep_len 200), ~60 % at L = 256.
-#ifndef D2D_GRU_PAD_COLLAPSE
-#define D2D_GRU_PAD_COLLAPSE 1
-#endif
 template <int HT, int IT, int KIND, bool SPLIT, bool COOP = false, bool LONGW = false>
 __global__ __launch_bounds__(256, 1) void gru_grad_kernel(GruArgs a) {
   constexpr int HW = 16 * HT, R3 = 3 * HW, RT = R3 + 4, SROWS = 2 * HW;
-  constexpr bool PADC = COOP && D2D_GRU_PAD_COLLAPSE != 0;
-  static_assert(!COOP || (HT == 4 && SPLIT && D2D_GRU_DH_BF16), "COOP: H in (32, 64], the split step, bf16 dh");
+  constexpr bool PADC = COOP;
+  static_assert(!COOP || (HT == 4 && SPLIT), "COOP: H in (32, 64], the split step");
   static_assert(COOP || !LONGW, "LONGW: the cooperative path");
   using SP = GruSplit<HT, IT>;
   using CR = CoopRegion<IT>;
   __shared__ __attribute__((aligned(16))) unsigned char whh_raw[SPLIT ? 16 * SP::WHH : 4 * R3 * HW];
   float* whh_s = reinterpret_cast<float*>(whh_raw);
   bf16x8* whh_b = reinterpret_cast<bf16x8*>(whh_raw);
-  // [unit u][gate row R], row stride R3 + 4 (COOP: none, the dh operands come from whh_b, whh_dh_frag)
+  // W_hh^T for dh_{j-1} = W_hh^T dg on v_mfma_f32_16x16x32_bf16: a two-way RNE bf16 split [W_h(4 rows) | W_m(4 rows)]
+  // per (unit, gate tile, lane group), so one A fragment serves two MFMAs (B = [g_h | g_h] and [g_m | g_m], ~2^-16
+  // relative per product).  Sized as HW rows of R3 + 4 floats (COOP: none, the dh operands come from whh_b, whh_dh_frag)
   __shared__ __attribute__((aligned(16))) float whhT_s[COOP ? 4 : HW * RT];
   // COOP: one staging region per wave (also its head-phase scratch; region 0 the final reduction
   // buffer) instead of the per-wave scratch blocks
@@ -471,7 +440,7 @@ __global__ __launch_bounds__(256, 1) void gru_grad_kernel(GruArgs a) {
   const int H = a.H, F = a.F, N = a.N, E = a.E, A = KIND == kGruValue ? 1 : a.A, L = a.L;
   uint16_t* creg = reinterpret_cast<uint16_t*>(creg_raw);
   float* sc = COOP ? reinterpret_cast<float*>(creg_raw + wave * CR::BYTES) : scr[COOP ? 0 : wave];
-  // DH_BF16: the transposed image as 16-byte entries [unit u][gate tile T * 4 + lane group][W_h x4 | W_m x4],
+  // the transposed image as 16-byte entries [unit u][gate tile T * 4 + lane group][W_h x4 | W_m x4],
   // TE entries per unit row (one of padding: the 16 lanes' A-fragment reads hit distinct banks)
   constexpr int TE = 3 * HT * 4 + 1;
   static_assert(HW * TE * 16 <= HW * RT * 4, "bf16 transposed image exceeds the fp32 one");
@@ -481,9 +450,7 @@ __global__ __launch_bounds__(256, 1) void gru_grad_kernel(GruArgs a) {
       const int R = idx / HW, c = idx - R * HW, G = R / HW, u = R - G * HW;
       const float v = (u < H && c < H) ? Whh[(size_t)(G * H + u) * H + c] : 0.f;
       if constexpr (!SPLIT) whh_s[swz<HW>(R, c)] = v;
-      if (!D2D_GRU_DH_BF16) whhT_s[c * RT + R] = v;
     }
-#if D2D_GRU_DH_BF16
     bf16x8* whhTb = reinterpret_cast<bf16x8*>(whhT_s);
     for (int idx = tid; idx < (COOP ? 0 : HW * 3 * HT * 4); idx += blockDim.x) {
       const int c = idx / (3 * HT * 4), rem = idx - c * (3 * HT * 4), T = rem >> 2, gg = rem & 3;
@@ -498,7 +465,6 @@ __global__ __launch_bounds__(256, 1) void gru_grad_kernel(GruArgs a) {
       const u32x4v e = {hw[0], hw[1], mw[0], mw[1]};
       whhTb[c * TE + T * 4 + gg] = __builtin_bit_cast(bf16x8, e);
     }
-#endif
     if constexpr (SPLIT) load_gru_split_images<HT, IT, COOP>(nullptr, whh_b, a.w, k, H, F, tid, blockDim.x);
   }
   f32x4 bhn[HT];
@@ -829,18 +795,10 @@ __global__ __launch_bounds__(256, 1) void gru_grad_kernel(GruArgs a) {
       }
       f32x4 rz[2 * HT], ni[HT], nh[HT];
       const int z = opaque_zero();
-#if D2D_GRU_ABLATE == 4
-#pragma unroll
-      for (int t = 0; t < HT; ++t) {
-        rz[t] = rz[HT + t] = f32x4{hp[t][0], hp[t][1], hp[t][2], hp[t][3]};
-        ni[t] = nh[t] = f32x4{x[0][0], x[0][1], x[0][2], x[0][3]};
-      }
-#else
       if constexpr (SPLIT)
         gru_preact_split<HT, IT, COOP>(wih_g + z, whh_b + z, lane, x, x_exact_step<IT>(a.ov, x), hp, bhn, rz, ni, nh, j == 0);
       else
         gru_preact<HT, IT, false>(wimg + z, whh_s + z, oi, oh, x, hp, bhn, rz, ni, nh, g, i, j == 0);
-#endif
       __builtin_amdgcn_sched_barrier(0);
       float drp[HT][4], dzp[HT][4], dnp[HT][4], dghn[HT][4], gz[HT][4];
 #pragma unroll
@@ -879,17 +837,14 @@ __global__ __launch_bounds__(256, 1) void gru_grad_kernel(GruArgs a) {
             reinterpret_cast<f32x4*>(hrow + row0 * 16)[v * 64 + lane] = reinterpret_cast<const f32x4*>(sc)[v * 64 + lane];
         lds_order();
       };
-#if D2D_GRU_ABLATE != 3
       if constexpr (!COOP) {
         stage_rows(drp, dzp, 0);
         stage_rows(dnp, dghn, 2 * HW);
         stage_rows(hp, nullptr, 4 * HW);
       }
-#endif
       __builtin_amdgcn_sched_barrier(0);
       // dh_{j-1} = g z + W_hh^T dgh: A fragments from the transposed image
       const float* wt = whhT_s + z;
-#if D2D_GRU_DH_BF16 && D2D_GRU_ABLATE != 2
       // dg split two ways once per step: B1 = [g_h | g_h], B2 = [g_m | g_m] per gate tile (rows 16T + 4g + r)
       bf16x8 gb1[3 * HT], gb2[3 * HT];
 #pragma unroll
@@ -904,34 +859,18 @@ __global__ __launch_bounds__(256, 1) void gru_grad_kernel(GruArgs a) {
         gb2[T] = __builtin_bit_cast(bf16x8, b2);
       }
       const bf16x8* wtb = reinterpret_cast<const bf16x8*>(wt);
-#endif
 #pragma unroll
       for (int t = 0; t < HT; ++t) {
         f32x4 dh = {gz[t][0], gz[t][1], gz[t][2], gz[t][3]};
-#if D2D_GRU_ABLATE == 2
-        dh += f32x4{drp[t][0], dzp[t][1], dghn[t][2], wt[lane]};
-#elif D2D_GRU_DH_BF16
 #pragma unroll
         for (int T = 0; T < 3 * HT; ++T) {
           const bf16x8 af = COOP ? whh_dh_frag<HT>(whh_b, T, t, g, i) : wtb[(16 * t + i) * TE + T * 4 + g];
           dh = mfma_bf16(af, gb1[T], dh);
           dh = mfma_bf16(af, gb2[T], dh);
         }
-#else
-#pragma unroll
-        for (int T = 0; T < 3 * HT; ++T) {
-          const f32x4 wv = *reinterpret_cast<const f32x4*>(wt + (16 * t + i) * RT + 16 * T + 4 * g);
-#pragma unroll
-          for (int s4 = 0; s4 < 4; ++s4) {
-            const float bv = T < HT ? drp[T][s4] : T < 2 * HT ? dzp[T - HT][s4] : dghn[T - 2 * HT][s4];
-            dh = mfma4(wv[s4], bv, dh);
-          }
-        }
-#endif
 #pragma unroll
         for (int r = 0; r < 4; ++r) gcur[t][r] = dh[r];
       }
-#if D2D_GRU_DH_BF16 && D2D_GRU_ABLATE != 2
       if constexpr (COOP) {
         // this step's rows as split pairs (r, z, n_h: the dh operands' splits; n_in and h_{j-1} here)
         uint32_t nih[HT][2], nim[HT][2], hph[HT][2], hpm[HT][2], xw[IT][2];
@@ -950,33 +889,29 @@ __global__ __launch_bounds__(256, 1) void gru_grad_kernel(GruArgs a) {
           *reinterpret_cast<uint2*>(own + coop_off(plane, i, 16 * t + 4 * g)) = make_uint2(w0, w1);
         };
         const int sA = 4 * g + (i >> 2), cq = 4 * (i & 3);  // this lane's transposing-read row / column
-        if (D2D_GRU_ABLATE != 6) {  // (ablation 6: no exchange)
-          __syncthreads();  // every wave has consumed the previous step's regions
-          {
+        __syncthreads();  // every wave has consumed the previous step's regions
 #pragma unroll
-            for (int t = 0; t < HT; ++t) {
-              const u32x4v rh = __builtin_bit_cast(u32x4v, gb1[t]), rm = __builtin_bit_cast(u32x4v, gb2[t]);
-              const u32x4v zh = __builtin_bit_cast(u32x4v, gb1[HT + t]), zm = __builtin_bit_cast(u32x4v, gb2[HT + t]);
-              const u32x4v nh_ = __builtin_bit_cast(u32x4v, gb1[2 * HT + t]), nm = __builtin_bit_cast(u32x4v, gb2[2 * HT + t]);
-              put(0, t, rh[0], rh[1]);
-              put(1, t, rm[0], rm[1]);
-              put(2, t, zh[0], zh[1]);
-              put(3, t, zm[0], zm[1]);
-              put(4, t, nih[t][0], nih[t][1]);
-              put(5, t, nim[t][0], nim[t][1]);
-              put(6, t, nh_[0], nh_[1]);
-              put(7, t, nm[0], nm[1]);
-              put(8, t, hph[t][0], hph[t][1]);
-              put(9, t, hpm[t][0], hpm[t][1]);
-            }
-#pragma unroll
-            for (int q = 0; q < IT; ++q)
-              *reinterpret_cast<uint2*>(own + coop_xoff<IT>(i, 16 * q + 4 * g)) = make_uint2(xw[q][0], xw[q][1]);
-          }
-          __syncthreads();
+        for (int t = 0; t < HT; ++t) {
+          const u32x4v rh = __builtin_bit_cast(u32x4v, gb1[t]), rm = __builtin_bit_cast(u32x4v, gb2[t]);
+          const u32x4v zh = __builtin_bit_cast(u32x4v, gb1[HT + t]), zm = __builtin_bit_cast(u32x4v, gb2[HT + t]);
+          const u32x4v nh_ = __builtin_bit_cast(u32x4v, gb1[2 * HT + t]), nm = __builtin_bit_cast(u32x4v, gb2[2 * HT + t]);
+          put(0, t, rh[0], rh[1]);
+          put(1, t, rm[0], rm[1]);
+          put(2, t, zh[0], zh[1]);
+          put(3, t, zm[0], zm[1]);
+          put(4, t, nih[t][0], nih[t][1]);
+          put(5, t, nim[t][0], nim[t][1]);
+          put(6, t, nh_[0], nh_[1]);
+          put(7, t, nm[0], nm[1]);
+          put(8, t, hph[t][0], hph[t][1]);
+          put(9, t, hpm[t][0], hpm[t][1]);
         }
+#pragma unroll
+        for (int q = 0; q < IT; ++q)
+          *reinterpret_cast<uint2*>(own + coop_xoff<IT>(i, 16 * q + 4 * g)) = make_uint2(xw[q][0], xw[q][1]);
+        __syncthreads();
 #pragma unroll 1
-        for (int src = 0; src < (D2D_GRU_ABLATE == 5 || D2D_GRU_ABLATE == 6 ? 0 : 4); ++src) {  // (ablation 5: barriers and writes only)
+        for (int src = 0; src < 4; ++src) {
           const uint16_t* reg = creg + src * CR::ELEMS;
           // every wave: its output tiles += the writer's 16 samples (k = sample 4g + q x split part).
           // All 18 fragment reads are issued before the first MFMA (one LDS wait per sub-phase).
@@ -1014,7 +949,6 @@ __global__ __launch_bounds__(256, 1) void gru_grad_kernel(GruArgs a) {
         if constexpr (LONGW)
           if (((L - 1 - j) % kFlushSteps) == kFlushSteps - 1 && j > 0) coop_flush();  // wave-uniform
       }
-#endif
     }
     if constexpr (PADC) {
       if (!ppass && jlo > 0) {  // dh_{jlo-1} of this tile's samples (lane columns) into the entry sums
@@ -1088,7 +1022,7 @@ __global__ __launch_bounds__(256, 1) void gru_grad_kernel(GruArgs a) {
       }
     };
 #pragma unroll 1
-    for (int tb0 = 0; tb0 < (COOP || D2D_GRU_ABLATE == 1 ? 0 : HT); tb0 += TBP) {
+    for (int tb0 = 0; tb0 < (COOP ? 0 : HT); tb0 += TBP) {
       f32x4 dwh[TBP][3][HT], dwi[TBP][3][IT];
 #pragma unroll
       for (int p = 0; p < TBP; ++p)
@@ -1134,7 +1068,6 @@ __global__ __launch_bounds__(256, 1) void gru_grad_kernel(GruArgs a) {
         if (j + 1 < L) load_fr(nxt, j + 1, tb0);
         float xt[IT][4];
         decode_xt(xt, cur);
-#if D2D_GRU_DW_BF16
         // B operands with the A fragments' k-slots (sample 4 s4 + g, part): h_{j-1} as [h h] and [m 0]
         // (the two MFMAs give a_h b_h + a_m b_h and a_h b_m), x (bf16-exact) as [x x]
         bf16x8 bh1[HT], bh2[HT], bx[IT];
@@ -1217,26 +1150,6 @@ __global__ __launch_bounds__(256, 1) void gru_grad_kernel(GruArgs a) {
               }
           }
         }
-#else
-#pragma unroll
-        for (int p = 0; p < TBP; ++p) {
-          if (tb0 + p >= HT) break;  // (odd HT: the last pass has one tile)
-#pragma unroll
-          for (int U = 0; U < HT; ++U)
-#pragma unroll
-            for (int g3 = 0; g3 < 3; ++g3) {
-              const f32x4 af = g3 < 2 ? cur.ai[p][g3] : cur.an[p];
-#pragma unroll
-              for (int s4 = 0; s4 < 4; ++s4) dwh[p][g3][U] = mfma4(af[s4], cur.bh[U][s4], dwh[p][g3][U]);
-            }
-#pragma unroll
-          for (int g3 = 0; g3 < 3; ++g3)
-#pragma unroll
-            for (int U = 0; U < IT; ++U)
-#pragma unroll
-              for (int s4 = 0; s4 < 4; ++s4) dwi[p][g3][U] = mfma4(cur.ai[p][g3][s4], xt[U][s4], dwi[p][g3][U]);
-        }
-#endif
         if ((j % kFlushSteps) == kFlushSteps - 1 && j + 1 < L) hist_flush();  // wave-uniform
       }
       hist_flush();
@@ -1377,6 +1290,8 @@ __global__ void gru_head_image_kernel(GruW w, int N, int H, int A, float* img) {
   img[idx] = head_img_elem<HT>(w, k, H, A, (int)(idx - (int64_t)k * SZ));
 }
 
+// the fp32 input image that gru_grad_kernel's SPLIT = false body reads.  d2d_gru_grad launches only SPLIT = true
+// (the split images, launch_wih_split), so nothing launches this kernel; it stays with the SPLIT = false body
 __global__ void gru_wih_image_kernel(GruW w, int N, int H, int F, int HW, int IW, float* img) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (int64_t)N * 3 * HW * IW) return;
@@ -1598,11 +1513,6 @@ static int gru_grad_blocks(int N, int64_t n_tiles) {
 // Float offsets of the grad kernel's workspace pieces (each rounded to 64 floats: 16-byte vector
 // accesses stay aligned): partials, h history, input images, head sums, head images, the per-step
 // gradient-row history, the weight-gradient sums.
-#ifndef D2D_GRU_GRAD_SPLIT
-#define D2D_GRU_GRAD_SPLIT 1  // 0: the fp32-MFMA step in the update kernel (ablation builds)
-#endif
-constexpr bool kGradSplit = D2D_GRU_GRAD_SPLIT != 0;
-
 struct GruWs {
   int64_t partial, hist, wimg, hacc, himg, ghist, gpart, total;
 };
@@ -1615,8 +1525,7 @@ std::atomic<int> g_gru_grad_history{0};
 // input tiles <= 3 (F + 1 <= 48: four staging regions + the W_hh image fit the 160 KB of LDS), the
 // compact record (bf16-exact inputs), the split step; `history` = the option's snapshot
 static bool gru_coop(int htp, int itp, bool u8, bool history) {
-  return !history && htp == 4 && itp <= 3 && u8 && D2D_GRU_GRAD_SPLIT && D2D_GRU_DH_BF16 &&
-         (D2D_GRU_ABLATE == 0 || D2D_GRU_ABLATE >= 5);
+  return !history && htp == 4 && itp <= 3 && u8;
 }
 static GruWs gru_ws_layout(int64_t G, int64_t N, int64_t P, int64_t L, int htp, int itp, bool coop) {
   auto up = [](int64_t v) { return (v + 63) / 64 * 64; };
@@ -1625,7 +1534,7 @@ static GruWs gru_ws_layout(int64_t G, int64_t N, int64_t P, int64_t L, int htp, 
   w.partial = 0;
   w.hist = up(G * N * P);
   // per wave: the tile's h history + the padding table (+ COOP: the padding-region entry sums, PADC)
-  w.wimg = w.hist + up(waves * (coop && D2D_GRU_PAD_COLLAPSE ? 3 : 2) * L * 64 * 4 * htp);
+  w.wimg = w.hist + up(waves * (coop ? 3 : 2) * L * 64 * 4 * htp);
   // fp32 input images [N][3 HW][16 itp] or the split ones [N][3 htp][CI][3 parts][64] 16-byte words
   const int64_t ci = (itp + 1) / 2;
   w.hacc = w.wimg + up(N * std::max<int64_t>(3 * HW * 16 * itp, 3 * htp * ci * 3 * 64 * 4));
@@ -1657,7 +1566,7 @@ extern "C" int64_t d2d_gru_grad_workspace(const d2d_gru_desc* d, int32_t T) {
 
 template <int HT, int IT>
 static void launch_grad_kind(const GruArgs& a, dim3 grid, hipStream_t s, bool coop) {
-  if constexpr (HT == 4 && IT <= 3 && kGradSplit && D2D_GRU_DH_BF16) {
+  if constexpr (HT == 4 && IT <= 3) {
     if (coop && a.L > kFlushSteps) {
       if (a.kind == kGruBernoulli)
         hipLaunchKernelGGL((gru_grad_kernel<HT, IT, kGruBernoulli, true, true, true>), grid, dim3(256), 0, s, a);
@@ -1676,10 +1585,10 @@ static void launch_grad_kind(const GruArgs& a, dim3 grid, hipStream_t s, bool co
     }
   }
   if (a.kind == kGruBernoulli)
-    hipLaunchKernelGGL((gru_grad_kernel<HT, IT, kGruBernoulli, kGradSplit>), grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL((gru_grad_kernel<HT, IT, kGruBernoulli, true>), grid, dim3(256), 0, s, a);
   else if (a.kind == kGruCategorical)
-    hipLaunchKernelGGL((gru_grad_kernel<HT, IT, kGruCategorical, kGradSplit>), grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((gru_grad_kernel<HT, IT, kGruValue, kGradSplit>), grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL((gru_grad_kernel<HT, IT, kGruCategorical, true>), grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((gru_grad_kernel<HT, IT, kGruValue, true>), grid, dim3(256), 0, s, a);
 }
 
 // the split W_ih images of all agents in the update workspace ([N][GruSplit::WIH] 16-byte words)
@@ -1763,15 +1672,9 @@ extern "C" int d2d_gru_grad(const d2d_gru_desc* d, int32_t T, const void* obs, c
   if (a.N == 0) return D2D_OK;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   {
-    if (kGradSplit) {
-      if (htp == 1) launch_wih_split<1>(a, itp, s);
-      else if (htp == 2) launch_wih_split<2>(a, itp, s);
-      else launch_wih_split<4>(a, itp, s);
-    } else {
-      const int64_t n = (int64_t)a.N * 3 * 16 * htp * 16 * itp;
-      hipLaunchKernelGGL(gru_wih_image_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a.w, a.N, a.H, a.F,
-                         16 * htp, 16 * itp, a.wimg);
-    }
+    if (htp == 1) launch_wih_split<1>(a, itp, s);
+    else if (htp == 2) launch_wih_split<2>(a, itp, s);
+    else launch_wih_split<4>(a, itp, s);
     const int64_t nh = (int64_t)a.N * (16 * htp * 16 * htp + 16 * 16 * htp + 16 * htp + 16);
     const dim3 gh((unsigned)((nh + 255) / 256));
     if (htp == 1) hipLaunchKernelGGL(gru_head_image_kernel<1>, gh, dim3(256), 0, s, a.w, a.N, a.H, a.A, a.himg);

@@ -27,7 +27,7 @@ struct MlpArgs {
 
 constexpr uint32_t kStreamPolicy = 3;
 // kModeValue: the split kernel's value-only instantiation (the iPPO critic as its own launch beside the actor:
-// policy_kernels.hip, D2D_POLICY_CRITIC_SPLIT)
+// policy_kernels.hip, D2D_OPT_POLICY_CRITIC_SPLIT)
 enum { kModeSample = 0, kModeDeterministic = 1, kModeForced = 2, kModeValue = 3, kModeRuntime = -1 };
 // The epilogue takes logits pre-multiplied by log2(e) (folded into W2, b2 by the split kernel) so
 // the softmax exponentials are bare v_exp_f32 (exp2, 1 ulp); the relative rounding of the scaled
@@ -79,14 +79,6 @@ __device__ __forceinline__ void load_obs_tile(float (&xf)[KS], const float* __re
 }
 
 
-// The Philox block policy_epilogue draws in sample mode for (env, agent k, action group ga) -- KIND 1 draws
-// group 0's block in every lane
-template <int KIND>
-__device__ __forceinline__ u32x4 policy_rng_block(const MlpArgs& a, int env, bool env_ok, int k, int ga, uint32_t rng) {
-  const uint32_t genv = (uint32_t)(a.env_base + (uint64_t)(env_ok ? env : 0));
-  return philox(genv, (uint32_t)k, rng, (kStreamPolicy << 24) | (KIND == 0 ? (uint32_t)ga : 0u), a.seed);
-}
-
 // Softmax over the A action logits of env i (action group ga holds actions 4ga..4ga+3 in lg),
 // sampling / forced / deterministic actions, log-prob and the stores (ippo.py:154-176).
 // HALF (A <= 8): each 32-lane half is its own env tile -- lanes 0-31 one tile, lanes 32-63 the
@@ -97,9 +89,8 @@ __device__ __forceinline__ u32x4 policy_rng_block(const MlpArgs& a, int env, boo
 // prefetch), or kModeRuntime (tested per launch from a.forced / a.deterministic).
 // PRE (forced mode): the forced mask / id was loaded ahead by the caller and arrives in `fpre`
 // (the split kernel's paired epilogue); otherwise the epilogue loads it itself.
-// RNG (sample mode): the lane's Philox block drawn ahead by the caller and passed in `rpre` -- the split
-// kernel draws it before its tile MFMAs so that the ten dependent rounds (20 v_mad_u64_u32) fill the MFMA issue
-// gaps instead of running as a serial chain after them; the same counter and key, so the same words.
+// RNG (sample mode): the lane's Philox block was drawn ahead by the caller and arrives in `rpre` (the same counter
+// and key, so the same words); otherwise the epilogue draws it itself, as every kernel does today.
 // AF != 0: the action count as a compile-time constant (a.A == AF; the split kernel's A = 8 instantiation, the
 // combinatorial envs' 8 channels): no per-action range selects
 template <int KIND, bool CRITIC, bool HALF = false, int MODE = kModeRuntime, bool PRE = false, bool SIGMOID = false,

@@ -22,7 +22,6 @@
 #include <atomic>
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
 
 #include "policy_split.h"
 
@@ -167,38 +166,10 @@ __device__ __forceinline__ void stage_record(float (&x)[KC][8], const uint32_t* 
   stage_record_words<KC>(x, d, sm);
 }
 
-#ifndef D2D_POLICY_RNG_EARLY
-// 1 (A/B): draw the paired epilogue's Philox block before the tile MFMAs instead of in the epilogue.  The
-// scheduler then issues the ten dependent rounds as one chain ahead of the MFMAs rather than in their gaps,
-// and the partner wave already hides the chain: 233.7 / 229.6 vs 232.7 / 227.5 us per 65,536-env slot
-// (r04i, two boxes' runs each) -- no gain, off
-#define D2D_POLICY_RNG_EARLY 0
-#endif
-#ifndef D2D_POLICY_ABLATE_NOREAD
-// != 0 only in tools/gpu/build_fusion_bound.sh's timing variant: every obs DMA aimed outside the buffer (zeros, no
-// memory traffic) -- the policy kernel without its read of the slot's record, i.e. what fusing the env step into
-// it could save at most (tools/gpu/fusion_bound.py)
-#define D2D_POLICY_ABLATE_NOREAD 0
-#endif
-#ifndef D2D_POLICY_ABLATE_FORCED_DMA
-// != 0 only in timing variants (tools/gpu/run_r06o.sh): forced mode without the forced-word DMA (every forced mask
-// reads as 0) -- what the forced words' DMA and extraction cost
-#define D2D_POLICY_ABLATE_FORCED_DMA 0
-#endif
-#ifndef D2D_POLICY_FORCED_PAIR
-// 1: one forced-word DMA per tile PAIR (lanes of group 0 bring tile t's words, group 1 tile t + 1's) instead of one per
-// tile (group 0 only)
-#define D2D_POLICY_FORCED_PAIR 1
-#endif
-#ifndef D2D_POLICY_ACTOR_WAVES
 // waves per SIMD of the actor-only record instantiation (137 VGPRs at 3; 4 needs <= 128)
-#define D2D_POLICY_ACTOR_WAVES 3
-#endif
-#ifndef D2D_POLICY_AF8_WAVES
-// the same for the A = 8 instantiations (AF = 8: 124-133 VGPRs at 3, 128 with no spills at 4 -- the forced mode
-// 128.2 / 129.9 -> 124.0 / 124.8 us per 65,536-env slot, sampled and deterministic unchanged; profiles/r06/policy_waves_ab.json)
-#define D2D_POLICY_AF8_WAVES 4
-#endif
+constexpr int kPolicyActorWaves = 3;
+// the same for the A = 8 instantiations (AF = 8: 128 VGPRs with no spills at 4; profiles/r06/policy_waves_ab.json)
+constexpr int kPolicyAf8Waves = 4;
 // KC = input chunks of 32 (F + 1 <= 32*KC), HT = hidden tiles of 16 (H <= 16*HT, even);
 // U8: the inputs are the env kernel's compact obs record (D2D_OBS_U8)
 // AF: the action count as a compile-time constant (0: a.A at run time; 8: the combinatorial envs' 8 channels)
@@ -207,7 +178,7 @@ template <int KC, int HT, int KIND, bool CRITIC, int MODE, bool U8, int AF = 0>
 // actor alone on the record (137 VGPRs: test(), D2D-PPO,
 // and iPPO training rollouts whose values come from the first epoch's critic pass); H in (64, 128] -- the
 // learners' default hidden_size 128 -- or F + 1 > 32: one wave / SIMD with the doubled weight fragments)
-__global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? ((CRITIC || !U8) ? 2 : AF == 8 ? D2D_POLICY_AF8_WAVES : D2D_POLICY_ACTOR_WAVES) : 1) void policy_split_kernel(MlpArgs a) {
+__global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? ((CRITIC || !U8) ? 2 : AF == 8 ? kPolicyAf8Waves : kPolicyActorWaves) : 1) void policy_split_kernel(MlpArgs a) {
   static_assert(HT % 2 == 0, "layer 2 consumes hidden tiles in pairs");
   // Philox step of the launch, read once before the obs pipeline starts (the optional device
   // offset of graph replays; a load inside the epilogue would add a wait to every tile pair)
@@ -234,13 +205,13 @@ __global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? ((CRITIC || !U8) ? 2 : 
   constexpr int DPC = chunk_dwords<U8>();
   __shared__ float ring[4][RING][KC][DPC][64];
   // forced mode: the forced-action words of each tile travel through the same DMA ring (one more
-  // buffer_load_dword ... lds per tile: lane i of group 0 brings the dword holding env i's byte), so no
+  // buffer_load_dword ... lds per tile PAIR: lane i of group 0 brings the dword holding env i's byte of tile t,
+  // group 1 tile t + 1's), so no
   // register load inside the tile loop drains the ring with vmcnt(0) and a wave can run any number of
   // tiles (one resident round).  Paired epilogue (A <= 8, one byte per cell) only; otherwise the DMA is
   // aimed outside the buffer (no traffic) and the epilogue loads its masks itself.
-  constexpr int FD = (MODE == kModeForced && !D2D_POLICY_ABLATE_FORCED_DMA) ? 1 : 0;
-  constexpr bool FP = D2D_POLICY_FORCED_PAIR != 0;           // one forced DMA per tile pair
-  constexpr int FSLOTS = FD ? (FP ? RING / 2 : RING) : 1;     // forced-word ring slots
+  constexpr int FD = MODE == kModeForced ? 1 : 0;
+  constexpr int FSLOTS = FD ? RING / 2 : 1;  // forced-word ring slots
   __shared__ uint32_t fring[4][FSLOTS][64];
   const int64_t fbytes = MODE == kModeForced ? ((int64_t)a.E * N * a.mask_bytes + 3) / 4 * 4 : 0;
   const __amdgpu_buffer_rsrc_t frsrc = __builtin_amdgcn_make_buffer_rsrc(
@@ -260,8 +231,7 @@ __global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? ((CRITIC || !U8) ? 2 : 
   auto issue = [&](int t, bool even) {
     // look-ahead tiles past this wave's last are still issued (the counted waits need a fixed
     // DMA count) but aimed outside the descriptor's range: no memory traffic, zeros
-    const uint32_t vo = (t < tiles && !D2D_POLICY_ABLATE_NOREAD) ? (uint32_t)((t * 16 + i) * N * RB) + (U8 ? 8 : 32) * g
-                                                                   : 0x80000000u;
+    const uint32_t vo = t < tiles ? (uint32_t)((t * 16 + i) * N * RB) + (U8 ? 8 : 32) * g : 0x80000000u;
 #pragma unroll
     for (int c = 0; c < KC; ++c)
 #pragma unroll
@@ -270,16 +240,16 @@ __global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? ((CRITIC || !U8) ? 2 : 
             rsrc, (__attribute__((address_space(3))) void*)&ring[wave][t % RING][c][j][0], 4,
             vo + (U8 ? 32 * c + 4 * j : 4 * (32 * c + j)), 0, 0, 0);
     if constexpr (FD) {
-      // 32-bit cell offsets: policy_mlp_args caps the forced buffer at 2 GiB.  FP: issued with the even tile of a pair
+      // 32-bit cell offsets: policy_mlp_args caps the forced buffer at 2 GiB.  Issued with the even tile of a pair
       // (wave-uniform branch), lane group 0 bringing tile t's words and group 1 tile t + 1's
-      if (!FP || even) {
-        const int tf = FP ? t + (g & 1) : t;
+      if (even) {
+        const int tf = t + (g & 1);
         const int env = wave_env0 + tf * 16 + i;
-        const uint32_t fo = (tf < tiles && (FP ? g < 2 : g == 0) && A <= 8 && env < a.E)
+        const uint32_t fo = (tf < tiles && g < 2 && A <= 8 && env < a.E)
                                 ? ((uint32_t)env * (uint32_t)N + (uint32_t)k) & ~3u
                                 : 0x80000000u;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(
-            frsrc, (__attribute__((address_space(3))) void*)&fring[wave][(FP ? t >> 1 : t) % FSLOTS][0], 4, fo, 0, 0, 0);
+            frsrc, (__attribute__((address_space(3))) void*)&fring[wave][(t >> 1) % FSLOTS][0], 4, fo, 0, 0, 0);
       }
     }
   };
@@ -300,7 +270,7 @@ __global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? ((CRITIC || !U8) ? 2 : 
   for (int tt = 0; tt < tiles; tt += 2) {
     issue(tt + RING - 2, true);
     issue(tt + RING - 1, false);
-    wait_vmem<(RING - 2) * KC * DPC + (FP ? (RING - 2) / 2 : RING - 2) * FD>();  // tiles tt, tt + 1 have landed
+    wait_vmem<(RING - 2) * KC * DPC + (RING - 2) / 2 * FD>();  // tiles tt, tt + 1 have landed
     __builtin_amdgcn_sched_barrier(0);        // no LDS read of the slots moves above the wait
     const int env0 = wave_env0 + tt * 16 + i, env1 = env0 + 16;
     // forced byte of this lane's paired-epilogue cell (env0 for groups 0-1, env1 for 2-3), read before the
@@ -308,18 +278,8 @@ __global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? ((CRITIC || !U8) ? 2 : 
     uint32_t fpre = 0;
     if constexpr (FD) {
       const int envc = g < 2 ? env0 : env1;
-      const uint32_t w = FP ? fring[wave][(tt >> 1) % FSLOTS][(g < 2 ? 0 : 16) + i]
-                            : fring[wave][(g < 2 ? tt : tt + 1) % FSLOTS][i];
+      const uint32_t w = fring[wave][(tt >> 1) % FSLOTS][(g < 2 ? 0 : 16) + i];
       fpre = (w >> (8 * (((uint32_t)(envc < a.E ? envc : 0) * (uint32_t)N + (uint32_t)k) & 3u))) & 0xFFu;
-    }
-    // the paired epilogue's Philox block, drawn here: inside the scheduling region of the tiles' MFMAs (the
-    // barrier below would otherwise keep it behind them as a serial chain of ten dependent rounds)
-    u32x4 rpre = {};
-    if constexpr (MODE == kModeSample && D2D_POLICY_RNG_EARLY) {
-      if (A <= 8) {
-        const int envc = g < 2 ? env0 : env1;
-        rpre = policy_rng_block<KIND>(a, envc, envc < a.E, k, g & 1, rng);
-      }
     }
     f32x4 lg0, lg1;
     float v0, v1;
@@ -340,8 +300,8 @@ __global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? ((CRITIC || !U8) ? 2 : 
 #pragma unroll
       for (int r = 0; r < 4; ++r) lgc[r] = uf(__builtin_amdgcn_permlane32_swap(fu(lg0[r]), fu(lg1[r]), false, false)[0]);
       const int envc = g < 2 ? env0 : env1;
-      policy_epilogue<KIND, CRITIC, true, MODE, MODE == kModeForced, false, MODE == kModeSample && D2D_POLICY_RNG_EARLY, AF>(
-          a, lgc, g < 2 ? v0 : v1, envc, envc < a.E, k, g, rng, fpre, rpre);
+      policy_epilogue<KIND, CRITIC, true, MODE, MODE == kModeForced, false, false, AF>(
+          a, lgc, g < 2 ? v0 : v1, envc, envc < a.E, k, g, rng, fpre);
     } else {
       policy_epilogue<KIND, CRITIC, false, MODE>(a, lg0, v0, env0, env0 < a.E, k, g, rng);
       policy_epilogue<KIND, CRITIC, false, MODE>(a, lg1, v1, env1, env1 < a.E, k, g, rng);
@@ -356,12 +316,9 @@ using namespace d2d;
 
 // option words set by d2d_set_option from any host thread: relaxed atomics, read once per call
 std::atomic<int> g_policy_f32_mfma{0};  // d2d_set_option(D2D_OPT_POLICY_F32_MFMA, 1): fp32-MFMA kernel
-#ifndef D2D_POLICY_CRITIC_SPLIT
 // the iPPO critic's weight fragments (48 + 16 registers at H = 64) hold the fused actor + critic kernel at two
 // waves per SIMD (224 VGPRs; the actor alone: 137); 1 = the value as a separate value-only launch
-#define D2D_POLICY_CRITIC_SPLIT 0
-#endif
-std::atomic<int> g_policy_critic_split{D2D_POLICY_CRITIC_SPLIT};  // d2d_set_option(D2D_OPT_POLICY_CRITIC_SPLIT, v)
+std::atomic<int> g_policy_critic_split{0};  // d2d_set_option(D2D_OPT_POLICY_CRITIC_SPLIT, v)
 
 template <int KS, int HT>
 static int launch_policy_f32(const MlpArgs& a, hipStream_t s) {
@@ -390,22 +347,12 @@ static int resident_blocks() {
   }();
   return n;
 }
-// (A/B) D2D_POLICY_SIZING=r: r resident rounds (0: the 256-envs-per-wave rule only); read once per process
-static int policy_sizing() {
-  static const int r = [] {
-    const char* e = getenv("D2D_POLICY_SIZING");
-    return e ? atoi(e) : 1;
-  }();
-  return r;
-}
 
 // envs per wave for one resident round of K (every wave's per-agent weight split amortised over all of its
 // tiles, no partial last round)
 template <auto K>
 static MlpArgs one_round(MlpArgs x) {
-  const int rounds = policy_sizing();
-  if (rounds <= 0) return x;
-  const int64_t per_agent = std::max<int64_t>(1, (int64_t)resident_blocks<K>() * rounds / x.N);
+  const int64_t per_agent = std::max<int64_t>(1, (int64_t)resident_blocks<K>() / x.N);
   int64_t epw = ((int64_t)x.E + 4 * per_agent - 1) / (4 * per_agent);
   epw = (epw + 31) / 32 * 32;
   // a wave's row offsets are 32-bit buffer offsets from its first row: epw * N row bytes stay below 2 GiB
@@ -427,13 +374,10 @@ static void launch_split_af(const MlpArgs& a, hipStream_t s) {
   else if (a.deterministic) launch_one<policy_split_kernel<KC, HT, KIND, CRITIC, kModeDeterministic, U8, AF>>(a, s);
   else launch_one<policy_split_kernel<KC, HT, KIND, CRITIC, kModeSample, U8, AF>>(a, s);
 }
-#ifndef D2D_POLICY_AFIX
-// 1: the record kernels of the combinatorial actor at A = 8 (the benched 8 channels) with the action count compile-time
-#define D2D_POLICY_AFIX 1
-#endif
 template <int KC, int HT, int KIND, bool CRITIC, bool U8>
 static void launch_split_fmt(const MlpArgs& a, hipStream_t s) {
-  if constexpr (KIND == 0 && U8 && D2D_POLICY_AFIX) {
+  // the record kernels of the combinatorial actor at A = 8 (the benched 8 channels) with the action count compile-time
+  if constexpr (KIND == 0 && U8) {
     if (a.A == 8) return launch_split_af<KC, HT, KIND, CRITIC, U8, 8>(a, s);
   }
   launch_split_af<KC, HT, KIND, CRITIC, U8, 0>(a, s);

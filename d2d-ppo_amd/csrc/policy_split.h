@@ -7,12 +7,6 @@
 #pragma once
 #include "policy_epilogue.h"
 
-#ifndef D2D_POLICY_L2_F32
-// 1 (A/B): actor layer 2 on v_mfma_f32_16x16x4_f32 straight from relu(H^T) (an exact fmaf chain, 16 MFMAs
-// of 32 cycles per tile) instead of the three-way split of relu(H^T) (88 VALU per tile) and 6 bf16 MFMAs
-#define D2D_POLICY_L2_F32 0
-#endif
-
 namespace d2d {
 
 // x[c][j] <- slot, then input F := 1.0 (layer-1 bias input) and inputs past F := 0
@@ -57,11 +51,7 @@ __device__ __forceinline__ void record_sign_masks(uint32_t (&sm)[KC][2], const u
 template <int KC, int HT, bool ACTOR, bool CRITIC>
 struct SplitNet {
   Parts w1p[ACTOR ? HT : 1][KC], v1p[CRITIC ? HT : 1][KC];
-#if D2D_POLICY_L2_F32
-  float w2f[HT][4];  // A operand of step (t, r): row = action i, k-slot g <-> hidden 16t + 4g + r
-#else
   Parts w2p[HT / 2];
-#endif
   float v2f[HT][4];
   f32x4 b2i;
   float c2;
@@ -94,15 +84,6 @@ struct SplitNet {
         v2f[t][r] = (CRITIC && hid < H) ? a.v2[(size_t)k * H + hid] : 0.f;
       }
     }
-#if D2D_POLICY_L2_F32
-#pragma unroll
-    for (int t = 0; t < HT; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int hid = 16 * t + 4 * g + r;
-        w2f[t][r] = (i < A && hid < H) ? a.w2[((size_t)k * A + i) * H + hid] * kLog2e : 0.f;
-      }
-#else
 #pragma unroll
     for (int c2i = 0; c2i < (ACTOR ? HT / 2 : 0); ++c2i) {
       // element j of lane group g <-> hidden 16 * (2 c2i + (j >> 2)) + 4 g + (j & 3): the
@@ -115,7 +96,6 @@ struct SplitNet {
       }
       w2p[c2i] = split3(wv);
     }
-#endif
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int act = 4 * g + r;
@@ -187,24 +167,6 @@ struct SplitNet {
 
     // ---- actor layer 2 on the accumulators of tile pairs (split, full six terms)
     lg = b2i;
-#if D2D_POLICY_L2_F32 == 1
-#pragma unroll
-    for (int t = 0; t < HT; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) lg = __builtin_amdgcn_mfma_f32_16x16x4f32(w2f[t][r], relu(ha[t][r]), lg, 0, 0, 0);
-#elif D2D_POLICY_L2_F32 == 2
-    {  // two independent accumulation chains (hidden tiles [0, HT/2) and [HT/2, HT)), summed once
-      f32x4 lh = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int t = 0; t < HT / 2; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          lg = __builtin_amdgcn_mfma_f32_16x16x4f32(w2f[t][r], relu(ha[t][r]), lg, 0, 0, 0);
-          lh = __builtin_amdgcn_mfma_f32_16x16x4f32(w2f[HT / 2 + t][r], relu(ha[HT / 2 + t][r]), lh, 0, 0, 0);
-        }
-      lg += lh;
-    }
-#else
 #pragma unroll
     for (int c2i = 0; c2i < (ACTOR ? HT / 2 : 0); ++c2i) {
       float hvals[8];
@@ -215,7 +177,6 @@ struct SplitNet {
       }
       lg = mfma_split(w2p[c2i], split3(hvals), false, lg);
     }
-#endif
     // ---- critic layer 2 (64 -> 1) on VALU
     value = 0.f;
     if constexpr (CRITIC) {

@@ -37,66 +37,13 @@
 #include <algorithm>
 #include <atomic>
 #include <cmath>
-#include <cstdlib>
 #include <type_traits>
 
 #include "ppo_epilogue.h"
 
-#ifndef D2D_UPD_ABLATE
-#define D2D_UPD_ABLATE 0  // != 0 only in tools/gpu/ablate_update.py's timing builds
-#endif
-#ifndef D2D_ACTOR_TR
-// actor on the compact record: the sample-on-rows layer 1 (HN = X . W1^T: 3 MFMAs per hidden tile
-// per half, its relu, the relu mask and the two-way split of relu(HN) for dW2) is not recomputed --
-// relu(HT)'s split parts, already made for the logits, are transposed through LDS with
-// ds_read_b64_tr_b16 into the dW2 operand layout, and their high part is the relu mask
-#define D2D_ACTOR_TR 1
-#endif
-#ifndef D2D_CRITIC_MASK
-// critic dV1 = sum_s dHv_s x_s^T with dHv = relu'(HV) * dv * v2 factored as
-//   dV1[h][:] = v2[h] * sum_s M[s][h] (dv_s x_s),   M = relu'(HV) in {0, 1}
-// M is exact in bf16 (no split); dv_s x_s is split two ways once per tile (16 values per lane)
-// instead of dHv (32), the relu' select and the dv * v2 products go, and v2 scales the sums once
-#define D2D_CRITIC_MASK 1
-#endif
-#ifndef D2D_LOGITS_SPLIT3
-#define D2D_LOGITS_SPLIT3 1  // 0 (timing A/B only): relu(HT) on the two-way split in the logits
-#endif
-#ifndef D2D_SPLIT_DOT2
-// split residuals v - (bf16 half): 2 (default since round 4) a v_perm / v_and plus one scalar v_sub_f32;
-// 1: one v_dot2c_f32_bf16 (round 3; fewer VALU but each one issues at a higher price beside the MFMAs:
-// actor 1.85 -> 1.83 ms, critic 0.776 -> 0.747 ms per 26 M agent-samples with 2, profiles/r04/upd_ab_sub2.json);
-// 0 (A/B only): the subtraction left to the compiler, which pairs it into v_pk_add_f32.  All three are exact
-// (v - h is representable), so the gradients are bitwise the same
-#define D2D_SPLIT_DOT2 2
-#endif
-#ifndef D2D_DW2_PAIRED
-// 1 (A/B only): record-path actor dW2^T = relu(H)^T . dZ over both 16-sample halves at once, k-slots =
-// 4 samples of half 0 | the same 4 of half 1: (h_h, h_m) x (dz_h, dz_m) in 3 MFMAs per hidden tile instead
-// of 2 x 2 with the duplicated [dz_h | dz_h] and zero-padded [dz_m | 0] operands.  ~1.5 % faster, but its
-// summation order differs from the fp32-row instantiation's, whose gradients the record path reproduces
-// bit for bit (tests/test_record_gpu.py); off
-#define D2D_DW2_PAIRED 0
-#endif
-#ifndef D2D_ACTOR_DZ_ONCE
-// record-path actor, paired epilogue (A <= 8): dZ split three ways ONCE in the epilogue's paired layout (both
-// halves at once) and the parts moved to each half's dH A operand by permlane32 swaps -- was a split per half of
-// the swapped values; dW2's dZ operand (two-way RNE = the first two parts) reaches the sample-on-k layout as bf16
-// through LDS with ds_read_b64_tr_b16 instead of an fp32 transpose and a second split; dH's relu mask applied to
-// the split parts with packed u16 ops.  Bitwise the same operands (and so gradients) as before
-#define D2D_ACTOR_DZ_ONCE 1
-#endif
-#ifndef D2D_UPD_WAVES
-#define D2D_UPD_WAVES 2  // waves per SIMD the update kernels are register-budgeted for (KC = 1)
-#endif
-#ifndef D2D_LOGITS_BF16
-// logits Z^T = W2 . relu(HT) on bf16 MFMAs: W2's three-way split against a three-way RNE split of
-// relu(HT) (every product term down to 2^-24), 3 x 16 instead of 4 x 32 MFMA cycles per hidden tile
-// (actor kernel 2.55 -> 2.44 ms per 26 M agent-samples); 0 = v_mfma_f32_16x16x4_f32 (exact fmaf chain)
-#define D2D_LOGITS_BF16 1
-#endif
-
 namespace d2d {
+
+constexpr int kUpdWaves = 2;  // waves per SIMD the update kernels are register-budgeted for (KC = 1)
 
 struct UpdArgs {
   int T, E, N, F, H, A, kind, mask_bytes;
@@ -154,50 +101,16 @@ __device__ __forceinline__ uint32_t bf16_lo_as_f32bits(uint32_t h) { return __bu
 struct Parts2x4 {
   uint32_t h[2], m[2];
 };
-// v minus the low / high bf16 of a packed pair on one v_dot2c_f32_bf16 (h.lo * -1 + h.hi * 0 + v):
-// the split residuals, exact (v - h is representable: h is v rounded to 8 bits); replaces the pair's
-// unpacking (v_perm + v_and) and subtraction.  The (-1, 0) / (0, -1) bf16 pairs are held in SGPRs: the
-// compiler encodes 0x0000BF80 as the inline constant -1.0, which the hardware does not read as that
-// pair (tools/gpu/probe/dot2_probe.hip: 65,487 of 65,536 residuals wrong; register and 32-bit literal
-// forms exact on all).  Contract: both values of the pair are finite.  The partner enters as h.x * 0, so
-// an inf / NaN partner makes the finite value's residual NaN (the per-value subtraction kept them apart);
-// the operands split here (relu(HT), dH, dZ, dv x) are finite for finite weights and inputs, and a
-// non-finite one already makes its gradient tensor non-finite through h itself, as in torch autograd.
-// Denormal values (|v| < 2^-126) may lose their residual (the probe prints what the hardware does):
-// an absolute error below 1.2e-38 per operand, far under any gradient's fp32 resolution.
-__device__ __forceinline__ uint32_t bf16_pair_neg1_lo() {
-  uint32_t c;
-  asm("s_mov_b32 %0, 0x0000bf80" : "=s"(c));
-  return c;
-}
-__device__ __forceinline__ uint32_t bf16_pair_neg1_hi() {
-  uint32_t c;
-  asm("s_mov_b32 %0, 0xbf800000" : "=s"(c));
-  return c;
-}
-// D2D_SPLIT_DOT2 == 2 (A/B): the residual as one v_perm / v_and plus one scalar v_sub_f32 (asm, so the
-// compiler cannot pair the subtractions into v_pk_add_f32)
+// v minus the low / high bf16 of a packed pair: the split residuals, exact (v - h is representable: h is v
+// rounded to 8 bits).  One v_perm / v_and to unpack plus one scalar v_sub_f32, written as asm so that the
+// compiler cannot pair the subtractions into v_pk_add_f32, which issues at a higher price beside the MFMAs
 __device__ __forceinline__ float sub_f32_asm(float a, float b) {
   float r;
   asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
   return r;
 }
-__device__ __forceinline__ float sub_bf16_lo(float v, uint32_t h) {
-#if D2D_SPLIT_DOT2 == 2
-  return sub_f32_asm(v, ffrom(bf16_lo_as_f32bits(h)));
-#elif !D2D_SPLIT_DOT2
-  return v - ffrom(bf16_lo_as_f32bits(h));
-#endif
-  return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, h), __builtin_bit_cast(bf16x2_t, bf16_pair_neg1_lo()), v, false);
-}
-__device__ __forceinline__ float sub_bf16_hi(float v, uint32_t h) {
-#if D2D_SPLIT_DOT2 == 2
-  return sub_f32_asm(v, ffrom(h & 0xFFFF0000u));
-#elif !D2D_SPLIT_DOT2
-  return v - ffrom(h & 0xFFFF0000u);
-#endif
-  return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, h), __builtin_bit_cast(bf16x2_t, bf16_pair_neg1_hi()), v, false);
-}
+__device__ __forceinline__ float sub_bf16_lo(float v, uint32_t h) { return sub_f32_asm(v, ffrom(bf16_lo_as_f32bits(h))); }
+__device__ __forceinline__ float sub_bf16_hi(float v, uint32_t h) { return sub_f32_asm(v, ffrom(h & 0xFFFF0000u)); }
 __device__ __forceinline__ Parts2x4 split2_4(const float (&v)[4]) {
   Parts2x4 o;
 #pragma unroll
@@ -439,11 +352,12 @@ __device__ __forceinline__ void lds_row(float (&v)[8], const float (*xw)[XS], in
 // KC = input chunks of 32 (F + 1 <= 32 KC), HT = hidden tiles of 16 (H <= 16 HT), A <= 16;
 // PAIR (A <= 8): one epilogue pass serves both halves (lanes 0-31 half 0, 32-63 half 1).
 // Products: layer 1 (both orientations) and dH on the exact bf16 split (the weight splits are
-// made once; x is bf16-exact on env observations, so 3 MFMAs per 16x16x32); the logits on
-// v_mfma_f32_16x16x4_f32 (an exact fmaf chain) straight from the accumulator registers; the
-// weight gradients dW1, dW2 on two-way RNE splits of their per-tile operands.
+// made once; x is bf16-exact on env observations, so 3 MFMAs per 16x16x32); the logits
+// Z^T = W2 . relu(HT) on bf16 MFMAs, W2's three-way split against a three-way RNE split of relu(HT)
+// (every product term down to 2^-24, 3 x 16 MFMA cycles per hidden tile); the weight gradients dW1,
+// dW2 on two-way RNE splits of their per-tile operands.
 template <int KC, int HT, int KIND, bool PAIR, bool U8, int AFIX = 0>
-__global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? D2D_UPD_WAVES : 1) void ppo_actor_grad_kernel(UpdArgs a) {
+__global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? kUpdWaves : 1) void ppo_actor_grad_kernel(UpdArgs a) {
   constexpr int QT = 2 * KC;  // input tiles of 16 in dW1
   const int lane = threadIdx.x & 63;
   const int g = lane >> 4, i = lane & 15;
@@ -451,9 +365,12 @@ __global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? D2D_UPD_WAVES : 1) void
   xcd_block(k, by);  // k = agent, by = sample-chunk group
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int H = a.H, A = AFIX > 0 ? AFIX : a.A, F = a.F;
-  // the transposed-relu(HT) path (D2D_ACTOR_TR): record inputs only (always bf16-exact, so the
-  // fractional-input body never runs) and the bf16 logits, whose split parts it transposes
-  constexpr bool TR = U8 && D2D_LOGITS_BF16 && D2D_ACTOR_TR;
+  // TR, the transposed-relu(HT) path on the compact record (always bf16-exact, so the fractional-input
+  // body never runs): the sample-on-rows layer 1 (HN = X . W1^T, its relu, the relu mask and the two-way
+  // split of relu(HN) for dW2) is not recomputed -- relu(HT)'s split parts, already made for the logits,
+  // are transposed through LDS with ds_read_b64_tr_b16 into the dW2 operand layout, and their high part
+  // is the relu mask
+  constexpr bool TR = U8;
 
   // ---- weights of agent k: the W1 split in registers; the two W2 operand sets (used once per
   // half per hidden tile) in LDS, shared by the workgroup's four waves
@@ -462,11 +379,7 @@ __global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? D2D_UPD_WAVES : 1) void
   // dH's three B operands [h|l], [m|h], [h|m], stored whole so one ds_read_b128 lands each in
   // the four consecutive registers the MFMA reads (no operand assembly moves)
   __shared__ __attribute__((aligned(16))) bf16x8 w2b_s[HT][3][64];
-#if D2D_LOGITS_BF16
   __shared__ __attribute__((aligned(16))) bf16x8 w2z_s[HT][3][64];       // Z^T's bf16 A operands [h|h], [m|m], [l|h]
-#else
-  __shared__ __attribute__((aligned(16))) float w2f_s[HT][64][4];        // Z^T's fp32 A operand
-#endif
   {
     const float* W1 = a.w1 + (size_t)k * H * F;
     const float* W2 = a.w2 + (size_t)k * A * H;
@@ -503,21 +416,10 @@ __global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? D2D_UPD_WAVES : 1) void
         const int hid = 16 * t + 4 * g + r;
         wz[r] = (i < A && hid < H) ? W2[(size_t)i * H + hid] : 0.f;
       }
-#if !D2D_LOGITS_BF16
-#pragma unroll
-      for (int r = 0; r < 4; ++r) w2f_s[t][lane][r] = wz[r];
-#else
-      {
-        const Parts4 pz = split3_4(wz);
-        w2z_s[t][0][lane] = cat(pz.h, pz.h);
-        w2z_s[t][1][lane] = cat(pz.m, pz.m);
-#if D2D_LOGITS_SPLIT3
-        w2z_s[t][2][lane] = cat(pz.l, pz.h);
-#else
-        w2z_s[t][2][lane] = cat(pz.l, pz.l);
-#endif
-      }
-#endif
+      const Parts4 pz = split3_4(wz);
+      w2z_s[t][0][lane] = cat(pz.h, pz.h);
+      w2z_s[t][1][lane] = cat(pz.m, pz.m);
+      w2z_s[t][2][lane] = cat(pz.l, pz.h);
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) b2i[r] = 4 * g + r < A ? a.b2[(size_t)k * A + 4 * g + r] : 0.f;
@@ -540,8 +442,11 @@ __global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? D2D_UPD_WAVES : 1) void
   constexpr int XS16 = 32 * KC + 4;  // bf16 rows of 8-byte multiples, 8 banks apart per 4 rows
   __shared__ __attribute__((aligned(16))) unsigned char xs_raw[TR ? 4 * 32 * XS16 * 2 : 4 * 32 * XS * 4];
   __shared__ __attribute__((aligned(16))) float dzt[4][2][16][20];
-  // DZ1 (D2D_ACTOR_DZ_ONCE): dZ's bf16 parts [half][part h / m][sample][16 actions] in the dzt space
-  constexpr bool DZ1 = TR && PAIR && D2D_ACTOR_DZ_ONCE;
+  // DZ1 (record path, paired epilogue): dZ is split three ways once in the epilogue's paired layout and the
+  // parts moved to each half's dH A operand by permlane32 swaps; dW2's dZ operand (two-way RNE = the first two
+  // parts) reaches the sample-on-k layout as bf16 through LDS with ds_read_b64_tr_b16; dH's relu mask is applied
+  // to the split parts with packed u16 ops.  dZ's bf16 parts [half][part h / m][sample][16 actions] in the dzt space
+  constexpr bool DZ1 = TR && PAIR;
   static_assert(2 * 2 * 16 * 16 * 2 <= 2 * 16 * 20 * 4, "the dZ part image fits the wave's dzt slice");
   constexpr int NV = HT * QT * 4 + HT * 4 + 4 + 2;
   // TR: relu(HT)'s split parts [wave][half][hidden tile][part][16 samples][16 hidden] bf16; the
@@ -637,43 +542,25 @@ __global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? D2D_UPD_WAVES : 1) void
         f32x4 z = b2i;
 #pragma unroll
         for (int t2 = 0; t2 < HT; ++t2) {
-#if !D2D_LOGITS_BF16
-          const f32x4 w2f = *reinterpret_cast<const f32x4*>(&w2f_s[t2][lane][0]);
+          // relu(HT) on a three-way RNE split: k-slots [h_m | h_h] against W2's [h|h], [m|m] parts and
+          // [h_h | h_l] against [l|h] -- every product down to 2^-24 in 3 MFMAs (the two-way split
+          // alone leaves ~2^-18 per logit, which the PPO gradient's cancellation over 10^5-10^7
+          // samples amplified to ~2e-5 of max|g| at the headline batch)
+          float hv[4];
 #pragma unroll
-          for (int r = 0; r < 4; ++r)
-#if D2D_UPD_ABLATE == 2  // timing ablation: logits without the fp32 MFMAs
-            z[r] += w2f[r] * relu(ht[t2][r]);
-#else
-            z = __builtin_amdgcn_mfma_f32_16x16x4f32(w2f[r], relu(ht[t2][r]), z, 0, 0, 0);
-#endif
-#else
-          {  // relu(HT) on a three-way RNE split: k-slots [h_m | h_h] against W2's [h|h], [m|m] parts and
-             // [h_h | h_l] against [l|h] -- every product down to 2^-24 in 3 MFMAs (the two-way split
-             // alone leaves ~2^-18 per logit, which the PPO gradient's cancellation over 10^5-10^7
-             // samples amplified to ~2e-5 of max|g| at the headline batch)
-            float hv[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) hv[r] = relu(ht[t2][r]);
-#if D2D_LOGITS_SPLIT3
-            const Parts4 hp = split3rne_4(hv);
-            // (part order m, h, l: the two operands can share h's registers)
-            const bf16x8 bh = cat(hp.m, hp.h), bl = cat(hp.h, hp.l);
-#else
-            const Parts2x4 hp = split2_4(hv);
-            const uint32_t z2[2] = {0u, 0u};
-            const bf16x8 bh = cat(hp.m, hp.h), bl = cat(hp.h, z2);
-#endif
-            z = mfma_bf16(w2z_s[t2][2][lane], bl, z);
-            z = mfma_bf16(w2z_s[t2][1][lane], bh, z);
-            z = mfma_bf16(w2z_s[t2][0][lane], bh, z);
-            if constexpr (TR) {
-              // the split parts to this half's image [part][sample i][hidden 4g .. 4g + 3]
-              uint16_t* im = trimg + (((wave * 2 + s) * HT + t2) * 2) * 256 + i * 16 + 4 * g;
-              *reinterpret_cast<uint2*>(im) = make_uint2(hp.h[0], hp.h[1]);
-              *reinterpret_cast<uint2*>(im + 256) = make_uint2(hp.m[0], hp.m[1]);
-            }
+          for (int r = 0; r < 4; ++r) hv[r] = relu(ht[t2][r]);
+          const Parts4 hp = split3rne_4(hv);
+          // (part order m, h, l: the two operands can share h's registers)
+          const bf16x8 bh = cat(hp.m, hp.h), bl = cat(hp.h, hp.l);
+          z = mfma_bf16(w2z_s[t2][2][lane], bl, z);
+          z = mfma_bf16(w2z_s[t2][1][lane], bh, z);
+          z = mfma_bf16(w2z_s[t2][0][lane], bh, z);
+          if constexpr (TR) {
+            // the split parts to this half's image [part][sample i][hidden 4g .. 4g + 3]
+            uint16_t* im = trimg + (((wave * 2 + s) * HT + t2) * 2) * 256 + i * 16 + 4 * g;
+            *reinterpret_cast<uint2*>(im) = make_uint2(hp.h[0], hp.h[1]);
+            *reinterpret_cast<uint2*>(im + 256) = make_uint2(hp.m[0], hp.m[1]);
           }
-#endif
         }
         zt[s] = z;
       }
@@ -686,11 +573,7 @@ __global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? D2D_UPD_WAVES : 1) void
 #pragma unroll
         for (int r = 0; r < 4; ++r) zc[r] = uf(__builtin_amdgcn_permlane32_swap(fu(zt[0][r]), fu(zt[1][r]), false, false)[0]);
         const int e = e0 + 16 * (g >> 1) + i;
-#if D2D_UPD_ABLATE == 1  // timing ablation: no epilogue (dz = z)
-        const f32x4 dzc = zc;
-#else
         const f32x4 dzc = ppo_dz<KIND, true, false, AFIX>(a, zc, cur.act[0], cur.lo[0], cur.w[0], e < a.E, g & 1, surr_acc, ent_acc);
-#endif
 #pragma unroll
         for (int r = 0; r < 4; ++r) db2[r].add(dzc[r]);
         // three RNE parts of this lane's 4 actions (half g >> 1, sample i, actions 4 (g & 1) .. + 3)
@@ -722,11 +605,7 @@ __global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? D2D_UPD_WAVES : 1) void
 #pragma unroll
         for (int r = 0; r < 4; ++r) zc[r] = uf(__builtin_amdgcn_permlane32_swap(fu(zt[0][r]), fu(zt[1][r]), false, false)[0]);
         const int e = e0 + 16 * (g >> 1) + i;
-#if D2D_UPD_ABLATE == 1  // timing ablation: no epilogue (dz = z)
-        const f32x4 dzc = zc;
-#else
         const f32x4 dzc = ppo_dz<KIND, true, false, AFIX>(a, zc, cur.act[0], cur.lo[0], cur.w[0], e < a.E, g & 1, surr_acc, ent_acc);
-#endif
 #pragma unroll
         for (int r = 0; r < 4; ++r) db2[r].add(dzc[r]);
         *reinterpret_cast<f32x4*>(&zb[g >> 1][i][4 * (g & 1)]) = dzc;
@@ -829,12 +708,10 @@ __global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? D2D_UPD_WAVES : 1) void
             acc = mfma_bf16(a_hm, w2b_s[t2][2][lane], acc);
             // relu' from the high part: nonzero exactly when relu(h) is (down to bf16's underflow at
             // ~1e-40, far below any pre-activation of normal-magnitude weights and inputs)
-#if !D2D_DW2_PAIRED
             const v4i16 tm = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4i16)(im + 256));
             const bf16x8 h_hm = cat_tr(th, tm);
             dw2[t2] = mfma_bf16(h_hm, bz2, dw2[t2]);
             dw2[t2] = mfma_bf16(h_hm, bz1, dw2[t2]);
-#endif
             bf16x8 d_hm;
             if constexpr (DZ1) {
               // split, then the mask on the packed parts: min(h-part bits, 1) is 0 / 1 per sample, and
@@ -895,39 +772,10 @@ __global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? D2D_UPD_WAVES : 1) void
 #pragma unroll
           for (int q = 0; q < QT; ++q) {
             if constexpr (!XE) dw1[t2][q] = mfma_bf16(d_hm, bx2[q], dw1[t2][q]);
-#if D2D_UPD_ABLATE != 3  // timing ablation 3: no dW1 products
             dw1[t2][q] = mfma_bf16(d_hm, bx1[q], dw1[t2][q]);
-#endif
           }
         }
       }
-#if D2D_DW2_PAIRED
-      if constexpr (TR) {
-        // dW2^T += relu(H)^T . dZ for both halves: lane (g, i) k-slots = samples 4g .. 4g + 3 of half 0,
-        // then the same of half 1 (relu(HT)'s parts from the transposed image, dZ from its LDS transpose)
-        float d0[4], d1[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          d0[r] = zb[0][4 * g + r][i];
-          d1[r] = zb[1][4 * g + r][i];
-        }
-        const Parts2x4 z0 = split2_4(d0), z1 = split2_4(d1);
-        const bf16x8 bzh = cat(z0.h, z1.h), bzm = cat(z0.m, z1.m);
-#pragma unroll
-        for (int t2 = 0; t2 < HT; ++t2) {
-          typedef __attribute__((address_space(3))) v4i16* lds_v4i16;
-          uint16_t* im0 = trimg + (((wave * 2 + 0) * HT + t2) * 2) * 256 + (4 * g + (i >> 2)) * 16 + 4 * (i & 3);
-          uint16_t* im1 = trimg + (((wave * 2 + 1) * HT + t2) * 2) * 256 + (4 * g + (i >> 2)) * 16 + 4 * (i & 3);
-          const bf16x8 ah = cat_tr(__builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4i16)(im0)),
-                                   __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4i16)(im1)));
-          const bf16x8 am = cat_tr(__builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4i16)(im0 + 256)),
-                                   __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4i16)(im1 + 256)));
-          dw2[t2] = mfma_bf16(ah, bzm, dw2[t2]);  // h_h dz_m
-          dw2[t2] = mfma_bf16(am, bzh, dw2[t2]);  // h_m dz_h
-          dw2[t2] = mfma_bf16(ah, bzh, dw2[t2]);  // h_h dz_h
-        }
-      }
-#endif
     };
     // Exact tiles run the branch-free XE body as they stream by (one tile of look-ahead: the
     // next tile's loads are issued as soon as this tile is staged); a tile with fractional inputs
@@ -1023,7 +871,10 @@ __global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? D2D_UPD_WAVES : 1) void
 // ------------------------------------------------------------------------ critic gradients
 // Value(x) = V2 relu(V1 x + c1) + c2, loss = mean (v - R)^2 (ippo.py:210-216).  Hidden layer in
 // the sample-on-rows orientation only: the 64 -> 1 layer is a per-lane product + a 16-lane row
-// sum, dV1 = dHv^T . X as in the actor.  a.w2 = V2 [N][1][H], a.b2 = c2 [N][1], a.weight = R.
+// sum.  dV1 = sum_s dHv_s x_s^T with dHv = relu'(HV) * dv * v2 is factored as
+//   dV1[h][:] = v2[h] * sum_s M[s][h] (dv_s x_s),   M = relu'(HV) in {0, 1}
+// M is exact in bf16 (no split), dv_s x_s is split two ways once per tile (16 values per lane), and v2
+// scales the sums once.  a.w2 = V2 [N][1][H], a.b2 = c2 [N][1], a.weight = R.
 template <int KC, bool U8>
 struct CriticIn {
   XRows<KC, U8> x;
@@ -1042,7 +893,7 @@ __device__ __forceinline__ void load_critic_in(CriticIn<KC, U8>& in, const UpdAr
 }
 
 template <int KC, int HT, bool U8>
-__global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? D2D_UPD_WAVES : 1) void ppo_critic_grad_kernel(UpdArgs a) {
+__global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? kUpdWaves : 1) void ppo_critic_grad_kernel(UpdArgs a) {
   constexpr int QT = 2 * KC;
   const int lane = threadIdx.x & 63;
   const int g = lane >> 4, i = lane & 15;
@@ -1126,10 +977,8 @@ __global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? D2D_UPD_WAVES : 1) void
     // the tile body (XE: bf16-exact inputs), deferred tiles as in the actor kernel
     auto body = [&](auto xe) {
       constexpr bool XE = decltype(xe)::value;
-#if D2D_CRITIC_MASK
       uint32_t mk[HT][2][2];  // relu' of HV as bf16 pairs [t2][half][r pair]
       float dvh[2][4];        // dL/dv of samples 16s + 4g + r
-#endif
       // this tile's sums of dL/db2, the loss and dL/dv2, added to the running sums once per tile
       float tdc = 0.f, tls = 0.f, tv2[HT];
 #pragma unroll
@@ -1167,11 +1016,7 @@ __global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? D2D_UPD_WAVES : 1) void
           float pv = 0.f;
 #pragma unroll
           for (int t2 = 0; t2 < HT; ++t2) pv = fmaf(relu(hv[t2][r]), v2f[t2], pv);
-#if D2D_UPD_ABLATE == 4  // timing ablation: no cross-lane value reduction
-          const float v = pv + c2;
-#else
           const float v = row_sum16(pv) + c2;
-#endif
           const bool ok = e0 + 16 * s + 4 * g + r < a.E;
           if (a.vout && i == 0 && ok)  // the value of every sample (d2d_ppo_critic_grad_values)
             a.vout[(int64_t)tslot * a.v_st[0] + (int64_t)(e0 + 16 * s + 4 * g + r) * a.v_st[1] + (int64_t)k * a.v_st[2]] = v;
@@ -1182,7 +1027,6 @@ __global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? D2D_UPD_WAVES : 1) void
           tls = fmaf(d, d, tls);
           tdc += dvs[r];
         }
-#if D2D_CRITIC_MASK
 #pragma unroll
         for (int t2 = 0; t2 < HT; ++t2) {
           float hr[4];
@@ -1213,50 +1057,9 @@ __global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? D2D_UPD_WAVES : 1) void
           const uint32_t m01[2] = {mk[t2][0][0], mk[t2][0][1]}, m23[2] = {mk[t2][1][0], mk[t2][1][1]};
           const bf16x8 am = cat(m01, m23);
           dv1[t2][q] = mfma_bf16(am, bm, dv1[t2][q]);
-#if D2D_UPD_ABLATE != 5  // timing ablation 5: no dV1 products
           dv1[t2][q] = mfma_bf16(am, bh, dv1[t2][q]);
-#endif
         }
       }
-      (void)XE;
-#else
-        // X sample-on-k for this half: B fragments with the split parts paired to dHv's
-        bf16x8 bx1[QT], bx2[QT];
-#pragma unroll
-        for (int q = 0; q < QT; ++q) {
-          float xc[4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) xc[r] = xw[16 * s + 4 * g + r][16 * q + i];
-          if constexpr (XE) {
-            const uint32_t xh2[2] = {pack_hi(xc[0], xc[1]), pack_hi(xc[2], xc[3])};
-            bx1[q] = cat(xh2, xh2);
-          } else {
-            const Parts2x4 xq = split2_4(xc);
-            const uint32_t z2[2] = {0u, 0u};
-            bx1[q] = cat(xq.h, xq.h);
-            bx2[q] = cat(xq.m, z2);
-          }
-        }
-#pragma unroll
-        for (int t2 = 0; t2 < HT; ++t2) {
-          float dh[4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            tv2[t2] = fmaf(dvs[r], relu(hv[t2][r]), tv2[t2]);
-            dh[r] = hv[t2][r] > 0.f ? dvs[r] * v2f[t2] : 0.f;
-          }
-          const Parts2x4 dp = split2_4(dh);
-          const bf16x8 d_hm = cat(dp.h, dp.m);
-#pragma unroll
-          for (int q = 0; q < QT; ++q) {
-            if constexpr (!XE) dv1[t2][q] = mfma_bf16(d_hm, bx2[q], dv1[t2][q]);
-#if D2D_UPD_ABLATE != 5  // timing ablation 5: no dV1 products
-            dv1[t2][q] = mfma_bf16(d_hm, bx1[q], dv1[t2][q]);
-#endif
-          }
-        }
-      }
-#endif
       dc2.add(tdc);
       loss_acc.add(tls);
 #pragma unroll
@@ -1299,12 +1102,8 @@ __global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? D2D_UPD_WAVES : 1) void
       for (int q = 0; q < QT; ++q)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-#if D2D_CRITIC_MASK
           const int hid = 16 * t + 4 * g + r;  // accumulator row: the factored-out v2[hid]
           acc[n++] = dv1[t][q][r] * (hid < H ? a.w2[(size_t)k * H + hid] : 0.f);
-#else
-          acc[n++] = dv1[t][q][r];
-#endif
         }
 #pragma unroll
     for (int t = 0; t < HT; ++t) acc[n++] = dv2[t].value();
@@ -1361,15 +1160,11 @@ __global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? D2D_UPD_WAVES : 1) void
 //   * M reaches the A layout (hidden on lanes) through LDS: relu(HVT)'s bf16 high halves (nonzero exactly when
 //     relu(h) >= 2^-133, the actor's relu-mask edge) written [sample][hidden] and read back transposed;
 //   * dv2[h] = sum_s dv_s relu(h_s) = sum_j V1ext[h][j] G[h][j] (relu(h_s) = M[s][h] (V1ext x_s)[h], V1ext = [V1 | c1]
-//     against x_s's bias column): from the workgroup's G partial once, no per-sample work (D2D_CRITIC_DV2_G; 0
-//     keeps per-sample fmas and Kahan sums for A/B).
+//     against x_s's bias column): from the workgroup's G partial once, no per-sample work.
 // Precision: forward as above (exact three-way V1 split, exact x); dv on a two-way RNE split (2^-17 relative per
 // term, as the sample-on-rows kernel's (dv x) split); x exact.  Fractional inputs (fp32 rows that are not
 // bf16-exact: the chsel env's 1/n ACKs) take the deferred body: x's residual parts in the forward, and
 // (dv_h + dv_m) x_h + dv_h x_m on x's two-way RNE split in dV1.
-#ifndef D2D_CRITIC_DV2_G
-#define D2D_CRITIC_DV2_G 1
-#endif
 template <int KC, bool U8>
 struct CriticInT {
   XRows<KC, U8> x;
@@ -1386,14 +1181,11 @@ __device__ __forceinline__ void load_critic_in_t(CriticInT<KC, U8>& in, const Up
 }
 
 
-#ifndef D2D_CRITIC_T_WAVES
-// waves per SIMD the hidden-on-rows critic is register-budgeted for (KC = 1, H <= 64, the record).  3 (168 VGPRs)
-// spills 18 registers, two scratch accesses per tile; on real rollouts 2 is faster: 0.708 / 0.712 -> 0.660 / 0.663 ms
-// per 26.2 M agent-samples, alternating A/B on one box (profiles/r05/critic_waves); random inputs had favoured 3
-#define D2D_CRITIC_T_WAVES 2
-#endif
+// waves per SIMD the hidden-on-rows critic is register-budgeted for (KC = 1, H <= 64, the record): 3 (168 VGPRs)
+// spills 18 registers, two scratch accesses per tile, and is slower on real rollouts (profiles/r05/critic_waves)
+constexpr int kCriticTWaves = 2;
 template <int KC, int HT, bool U8>
-__global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? (U8 ? D2D_CRITIC_T_WAVES : D2D_UPD_WAVES) : 1) void ppo_critic_grad_t_kernel(UpdArgs a) {
+__global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? (U8 ? kCriticTWaves : kUpdWaves) : 1) void ppo_critic_grad_t_kernel(UpdArgs a) {
   constexpr int QT = 2 * KC;
   const int lane = threadIdx.x & 63;
   const int g = lane >> 4, i = lane & 15;
@@ -1436,9 +1228,6 @@ __global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? (U8 ? D2D_CRITIC_T_WAVE
 #pragma unroll
     for (int q = 0; q < QT; ++q) dv1[t][q] = f32x4{0.f, 0.f, 0.f, 0.f};
   KahanSum dc2, loss_acc;
-#if !D2D_CRITIC_DV2_G
-  KahanSum dv2k[HT][4];
-#endif
 
   // per-wave LDS: the tile's inputs as bf16 high parts (exact on the tiles the main body runs) and, for the
   // deferred fractional tiles of fp32 rows, as fp32; relu(HVT)'s high halves [half][t2][sample][hidden]; dv's
@@ -1449,7 +1238,7 @@ __global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? (U8 ? D2D_CRITIC_T_WAVE
   __shared__ __attribute__((aligned(16))) uint16_t xs16[4][32][XS16];
   constexpr int X32B = U8 ? 16 : 4 * 32 * XS * 4;
   __shared__ __attribute__((aligned(16))) unsigned char xs32_raw[X32B];
-  constexpr int NV = HT * QT * 4 + 2 + (D2D_CRITIC_DV2_G ? 0 : HT * 4);
+  constexpr int NV = HT * QT * 4 + 2;
   constexpr int MIMGB = 4 * 2 * HT * 256 * 2;
   constexpr int RAWB = MIMGB > NV * 64 * 4 ? MIMGB : NV * 64 * 4;
   __shared__ __attribute__((aligned(16))) unsigned char raw[RAWB];
@@ -1506,13 +1295,6 @@ __global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? (U8 ? D2D_CRITIC_T_WAVE
       constexpr bool XE = decltype(xe)::value;
       float dvv[2];  // dL/dv of samples i and 16 + i
       float tdc = 0.f, tls = 0.f;
-#if !D2D_CRITIC_DV2_G
-      float tv2[HT][4];
-#pragma unroll
-      for (int t2 = 0; t2 < HT; ++t2)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) tv2[t2][r] = 0.f;
-#endif
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         // HVT = V1 . X^T (hidden 16 t2 + 4 g + r on rows, sample 16 s + i on lanes)
@@ -1557,17 +1339,9 @@ __global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? (U8 ? D2D_CRITIC_T_WAVE
           }
           *reinterpret_cast<uint2*>(mimg + (s * HT + t2) * 256 + i * 16 + 4 * g) =
               make_uint2(pack_hi(hr[0], hr[1]), pack_hi(hr[2], hr[3]));
-#if !D2D_CRITIC_DV2_G
-#pragma unroll
-          for (int r = 0; r < 4; ++r) hv[t2][r] = hr[r];
-#endif
         }
         const float pv = (pv4[0] + pv4[1]) + (pv4[2] + pv4[3]);
-#if D2D_UPD_ABLATE == 4  // timing ablation: no cross-lane value reduction
-        const float v = pv + c2;
-#else
         const float v = group_sum(pv) + c2;
-#endif
         const bool ok = e0 + 16 * s + i < a.E;
         // the critic's value of every sample (iPPO's deferred rollout values, d2d_ppo_critic_grad_values)
         if (a.vout && g == 0 && ok)
@@ -1577,12 +1351,6 @@ __global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? (U8 ? D2D_CRITIC_T_WAVE
         dvv[s] = 2.f * a.scale * d;
         tls = fmaf(d, d, tls);
         tdc += dvv[s];
-#if !D2D_CRITIC_DV2_G
-#pragma unroll
-        for (int t2 = 0; t2 < HT; ++t2)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) tv2[t2][r] = fmaf(dvv[s], hv[t2][r], tv2[t2][r]);
-#endif
       }
       // dv's two-way RNE split, shared through LDS: [part][half][sample] (every lane group writes the same value)
       {
@@ -1642,19 +1410,11 @@ __global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? (U8 ? D2D_CRITIC_T_WAVE
         }
 #pragma unroll
         for (int q = 0; q < QT; ++q) dv1[t2][q] = mfma_bf16(Am, bx[q], dv1[t2][q]);     // dv_m x_h
-#if D2D_UPD_ABLATE != 5  // timing ablation 5: no dV1 products
 #pragma unroll
         for (int q = 0; q < QT; ++q) dv1[t2][q] = mfma_bf16(Ah, bx[q], dv1[t2][q]);     // dv_h x_h
-#endif
       }
       dc2.add(tdc);
       loss_acc.add(tls);
-#if !D2D_CRITIC_DV2_G
-#pragma unroll
-      for (int t2 = 0; t2 < HT; ++t2)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) dv2k[t2][r].add(tv2[t2][r]);
-#endif
     };
     CriticInT<KC, U8> in;
     bool deferred = false;
@@ -1698,12 +1458,6 @@ __global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? (U8 ? D2D_CRITIC_T_WAVE
         for (int r = 0; r < 4; ++r) acc[n++] = dv1[t][q][r];
     acc[n++] = dc2.value();
     acc[n++] = loss_acc.value();
-#if !D2D_CRITIC_DV2_G
-#pragma unroll
-    for (int t = 0; t < HT; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[n++] = dv2k[t][r].value();
-#endif
   }
   __syncthreads();  // every wave is past its last read of the relu image the reduction buffer aliases
   reduce_waves<NV>(acc, red, wave, lane);
@@ -1726,21 +1480,13 @@ __global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? (U8 ? D2D_CRITIC_T_WAVE
         if (hid < H) {
           if (col < F) out[hid * F + col] = G * v2r[t][r];
           else if (col == F) out[OB1 + hid] = G * v2r[t][r];
-#if D2D_CRITIC_DV2_G
           const float w = col < F ? V1[(size_t)hid * F + col] : col == F ? a.b1[(size_t)k * H + hid] : 0.f;
           dv2p[t][r] = fmaf(w, G, dv2p[t][r]);
-#endif
         }
       }
   }
   const float dcs = row_sum16(acc[n]);
   const float ls = row_sum16(acc[n + 1]);
-#if !D2D_CRITIC_DV2_G
-#pragma unroll
-  for (int t = 0; t < HT; ++t)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) dv2p[t][r] = acc[n + 2 + 4 * t + r];
-#endif
 #pragma unroll
   for (int t = 0; t < HT; ++t)
 #pragma unroll
@@ -1790,26 +1536,10 @@ static int64_t tensor_extent(const int64_t (&st)[3], int T, int E, int N) {
 // length: at the 65,536-env batch 16 workgroups per agent left 6,400 tiles per wave and dW2 at 4x torch fp32's
 // error against float64 (tools/gpu/ppo_grads_full_batch.py); the G partials are summed by update_reduce_kernel
 // (G x N x P floats, 0.26 GB at that batch).
-#ifndef D2D_UPD_MAX_WAVE_TILES
-#define D2D_UPD_MAX_WAVE_TILES 256
-#endif
-constexpr int64_t kMaxWaveTiles = D2D_UPD_MAX_WAVE_TILES;
-#ifndef D2D_UPD_MIN_ROUNDS
-// at least this many resident rounds of workgroups per launch (a small batch's waves then run fewer tiles each and the
-// last round's stragglers cost less); D2D_UPD_MIN_ROUNDS in the environment overrides it (A/B, read once per process)
-#define D2D_UPD_MIN_ROUNDS 1
-#endif
-static int upd_min_rounds() {
-  static const int r = [] {
-    const char* e = getenv("D2D_UPD_MIN_ROUNDS");
-    const int v = e ? atoi(e) : D2D_UPD_MIN_ROUNDS;
-    return v < 1 ? 1 : v > 8 ? 8 : v;
-  }();
-  return r;
-}
+constexpr int64_t kMaxWaveTiles = 256;  // bounds the fp32 accumulation chain of a wave (see above)
 static int update_blocks(int N, int64_t n_tiles, int resident) {
   const int64_t need = (int64_t)N * ((n_tiles + 4 * kMaxWaveTiles - 1) / (4 * kMaxWaveTiles));
-  const int64_t rounds = std::max<int64_t>(upd_min_rounds(), (need + resident - 1) / resident);
+  const int64_t rounds = std::max<int64_t>(1, (need + resident - 1) / resident);  // at least one resident round
   const int64_t G = (rounds * resident + N - 1) / N;
   // (grid.y <= 65535: past that, more tiles per wave)
   return (int)std::max<int64_t>(1, std::min<int64_t>({G, (n_tiles + 3) / 4, 65535}));
@@ -1836,7 +1566,7 @@ static int upd_resident() {
 // the workspace bound for any kernel's G: rounds x resident < need + resident <= need + 8 workgroups per CU
 static int update_blocks_bound(int N, int64_t n_tiles) {
   const int64_t need = (int64_t)N * ((n_tiles + 4 * kMaxWaveTiles - 1) / (4 * kMaxWaveTiles));
-  const int64_t G = (std::max<int64_t>(need + 8 * (int64_t)cu_count(), (int64_t)upd_min_rounds() * 8 * cu_count()) + N - 1) / N;
+  const int64_t G = (need + 8 * (int64_t)cu_count() + N - 1) / N;
   return (int)std::max<int64_t>(1, std::min<int64_t>({G, (n_tiles + 3) / 4, 65535}));
 }
 

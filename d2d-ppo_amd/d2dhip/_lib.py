@@ -10,30 +10,26 @@ import ctypes
 import os
 import sys
 
-import torch  # noqa: F401  (must be imported before the HIP library is loaded)
-
 PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(PKG_DIR, "lib", "libd2dhip.so")
-# A/B timing builds only (tools/gpu/ablate_update.py): another in-tree build of the same library.
-# Those builds drop parts of the update on purpose (wrong gradients), so the variable is honoured
-# only together with an explicit D2D_ALLOW_ABLATION=1, loudly, and the learners refuse to train on it.
-# "asan" is the host-sanitizer build (make -C d2d-ppo_amd asan, run only by tests/test_sanitizers_cpu.py
-# on a GPU-less host): correct, but never a product library either.
+# D2D_LIB_VARIANT=asan selects the host-sanitizer build (make -C d2d-ppo_amd asan, run only by
+# tests/test_sanitizers_cpu.py on a GPU-less host): correct, but not a product library, so the learners
+# refuse to train on it.  The ablation builds the variable once selected were retired.
 VARIANT = os.environ.get("D2D_LIB_VARIANT") or None
 if VARIANT:
-    if VARIANT != "asan" and os.environ.get("D2D_ALLOW_ABLATION") != "1":
-        raise RuntimeError(f"D2D_LIB_VARIANT={VARIANT} selects an ablation build of libd2dhip (wrong results "
-                           f"by design); set D2D_ALLOW_ABLATION=1 as well to load it, or unset it")
-    LIB_PATH = (os.path.join(PKG_DIR, "build", "asan", "libd2dhip_asan.so") if VARIANT == "asan"
-                else os.path.join(PKG_DIR, "lib", f"libd2dhip_{VARIANT}.so"))
-    print(f"[d2dhip] WARNING: loading {'sanitizer' if VARIANT == 'asan' else 'ablation'} build {LIB_PATH} "
-          f"(not a product library)", file=sys.stderr, flush=True)
+    if VARIANT != "asan":
+        raise RuntimeError(f"D2D_LIB_VARIANT={VARIANT}: ablation builds of libd2dhip were retired; the only "
+                           f"variant is 'asan' (unset the variable for the product library)")
+    LIB_PATH = os.path.join(PKG_DIR, "build", "asan", "libd2dhip_asan.so")
+    print(f"[d2dhip] WARNING: loading sanitizer build {LIB_PATH} (not a product library)", file=sys.stderr, flush=True)
+
+import torch  # noqa: F401, E402  (must be imported before the HIP library is loaded)
 
 
 def refuse_ablation(what):
-    """Product entry points (training, smoke) must not run on an ablation build."""
+    """Product entry points (training, smoke) must run on the product library."""
     if VARIANT:
-        raise RuntimeError(f"{what} refuses the ablation build libd2dhip_{VARIANT}.so (D2D_LIB_VARIANT)")
+        raise RuntimeError(f"{what} refuses libd2dhip_{VARIANT}.so (D2D_LIB_VARIANT): not a product library")
 
 D2D_ENV_COMBINATORIAL, D2D_ENV_CHANNEL_SELECTION, D2D_ENV_SINGLE = 0, 1, 2
 D2D_ARRIVAL_POISSON, D2D_ARRIVAL_SCHEDULED_BERNOULLI, D2D_ARRIVAL_NONE = 0, 1, 2

@@ -516,7 +516,7 @@ int d2d_rdqn_grad(const d2d_rdqn_desc* desc, const float* obs, const int32_t* sa
                   int64_t workspace_floats, void* stream);
 
 /* Process-wide tuning options (not part of the reference interface).
- * D2D_OPT_NT_STORES: 1 = write obs/state with non-temporal (streaming) stores.
+ * D2D_OPT_NT_STORES: 1 = write obs/state with non-temporal (streaming) stores.  Default: 0.
  * D2D_OPT_POLICY_F32_MFMA: 1 = d2d_policy_mlp_step on v_mfma_f32_16x16x4_f32 instead of the
  *   default exact-split bf16 MFMA kernel (both fp32-accurate; for A/B timing and tests).
  * D2D_OPT_GRU_GRAD_HISTORY: 1 = d2d_gru_grad accumulates the weight gradients through the per-wave
@@ -526,7 +526,7 @@ int d2d_rdqn_grad(const d2d_rdqn_desc* desc, const float* obs, const int32_t* sa
  *   for a buffer sized under the other setting).
  * D2D_OPT_POLICY_CRITIC_SPLIT: d2d_policy_mlp_step with a critic runs the actor and the critic value as two
  *   launches of the split kernel (1) or as one fused launch (0); the same arithmetic either way (bitwise
- *   identical actions, log-probs and values).  Default: policy_kernels.hip's D2D_POLICY_CRITIC_SPLIT.
+ *   identical actions, log-probs and values).  Default: 0.
  * D2D_OPT_CRITIC_GRAD_ROWS: 1 = d2d_ppo_critic_grad on the sample-on-rows kernel of rounds 2-4 (A/B; the same
  *   gradients within fp32 rounding); 0 (default) = the hidden-on-rows kernel (update_kernels.hip).
  * D2D_OPT_FUSED_SLICE: envs per workgroup of d2d_comb_policy_fused_step, 32 (0 = default) or 64 (A/B; the same

@@ -5,6 +5,8 @@ mask packing, reference-API attributes) behaves like the reference."""
 import ctypes
 import os
 import re
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -136,6 +138,39 @@ def test_abi14_argument_checks():
     assert lib.d2d_central_critic_dw1(64, 64, 100, 104, ctypes.c_void_p(24), w, w, 10 ** 6, w, None) == -1  # misaligned
     assert lib.d2d_central_critic_dw1(64, 64, 100, 104, w, w, w, 1, w, None) == -1  # workspace too small
     assert b"d2d_central_critic_dw1_workspace" in lib.d2d_last_error()
+
+
+def _child(code, **env_set):
+    """Run `code` in a fresh interpreter with the package on its path: the library fixed its sizing once per
+    process and d2dhip._lib reads D2D_LIB_VARIANT at import.  env_set: variables to set (None: to remove)."""
+    env = {**os.environ, **{k: v for k, v in env_set.items() if v is not None}}
+    for k in (k for k, v in env_set.items() if v is None):
+        env.pop(k, None)
+    pre = f"import sys; sys.path[:0] = [{ROOT!r}, {os.path.join(ROOT, 'd2d-ppo_amd')!r}]; "
+    return subprocess.run([sys.executable, "-c", pre + code], cwd=ROOT, env=env, capture_output=True, text=True,
+                          timeout=120)
+
+
+def test_workspace_size_ignores_environment():
+    """The update grid, and with it the fixed-order reduction partition and the workspace bound, depends on the
+    arguments and the device alone: D2D_UPD_MIN_ROUNDS, which the library once read, changes nothing (with it the
+    bound was G = 2048 workgroups per agent against 1032 at the 256-CU fallback of a GPU-less host)."""
+    import d2dhip
+    # (the library alone, without torch: the size query needs no tensor and the child starts in milliseconds)
+    code = (f"import ctypes; f = ctypes.CDLL({d2dhip.LIB_PATH!r}).d2d_ppo_workspace; f.restype = ctypes.c_int64; "
+            f"print('WS', f(2, 64, 4096, 30, 64, 8))")
+    got = []
+    for rounds in (None, "8"):
+        r = _child(code, D2D_UPD_MIN_ROUNDS=rounds)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        got.append(int(re.search(r"^WS (\d+)$", r.stdout, re.M).group(1)))
+    assert got[0] > 0 and got[0] == got[1], got
+
+
+def test_retired_library_variants_are_refused():
+    """The ablation builds D2D_LIB_VARIANT selected were retired: only the host-sanitizer build is left."""
+    r = _child("import d2dhip._lib", D2D_LIB_VARIANT="upd3", D2D_ALLOW_ABLATION="1")
+    assert r.returncode != 0 and "RuntimeError" in r.stderr, r.stdout[-2000:] + r.stderr[-3000:]
 
 
 def test_d2denv_record_signed_masks():

@@ -2,12 +2,11 @@
 batch (64 agents x 8 channels x 65,536 envs, the compact record, H = 64): what a kernel that runs the env step and
 the next slot's policy together could save at most is (i) the policy kernel's read of the slot's record, which
 the env kernel has just written (the record must still be written: it is the rollout buffer the update reads),
-and (ii) the launch boundary between the two kernels.  Measured here:
-  * the training slot as iPPO runs it (actor-only policy kernel, then the env kernel), per-kernel HIP events and
-    the slot's wall time per step (the boundary = slot - policy - env);
-  * the same policy launches with every record DMA aimed outside the buffer (libd2dhip_noread.so, run in a child
-    process: the same instructions, no memory traffic for the obs) -- policy_us - noread_us bounds (i).
-usage (GPU box, after bash tools/gpu/build_fusion_bound.sh): python3 tools/gpu/fusion_bound.py"""
+and (ii) the launch boundary between the two kernels.  Measured here: the training slot as iPPO runs it
+(actor-only policy kernel, then the env kernel), per-kernel HIP events and the slot's wall time per step
+(the boundary (ii) = slot - policy - env).  Part (i) was measured once with a build of the policy kernel whose
+record DMAs were aimed outside the buffer (DESIGN.md "retired switches"; the figures are in DESIGN §10).
+usage (GPU box): python3 tools/gpu/fusion_bound.py"""
 import json
 import os
 import subprocess
@@ -58,12 +57,8 @@ print(json.dumps(res))
 '''
 
 
-def run(variant):
-    env = dict(os.environ)
-    if variant:
-        env.update({"D2D_LIB_VARIANT": variant, "D2D_ALLOW_ABLATION": "1"})
-    r = subprocess.run([sys.executable, "-c", CHILD.format(root=ROOT)], env=env, capture_output=True, text=True,
-                       timeout=300)
+def run():
+    r = subprocess.run([sys.executable, "-c", CHILD.format(root=ROOT)], capture_output=True, text=True, timeout=300)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     if not lines:
         raise RuntimeError(r.stderr[-2000:])
@@ -71,16 +66,11 @@ def run(variant):
 
 
 if __name__ == "__main__":
-    base, noread = run(None), run("noread")
-    rec_bytes = 65536 * 64 * 32
-    a, n = base["actor"], noread["actor"]
+    base = run()
+    a = base["actor"]
     out = {"workload": "64 agents x 8 channels x 65,536 envs, compact record (32 B/agent-step), iPPO MLP H = 64",
-           "base": base, "noread": noread,
-           "record_read_us": a["policy_us"] - n["policy_us"],
-           "record_bytes_per_slot": rec_bytes,
-           "record_read_GBps": rec_bytes / max(a["policy_us"] - n["policy_us"], 1e-9) / 1e3,
+           "base": base,
+           "record_bytes_per_slot": 65536 * 64 * 32,
            "boundary_us": a["slot_us"] - a["policy_us"] - a["env_us"],
-           "fusion_saves_at_most_us": (a["policy_us"] - n["policy_us"]) + (a["slot_us"] - a["policy_us"] - a["env_us"]),
            "slot_us": a["slot_us"]}
-    out["fusion_saves_at_most_frac"] = out["fusion_saves_at_most_us"] / a["slot_us"]
     print(json.dumps(out, indent=1))

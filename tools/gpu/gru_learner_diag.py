@@ -1,7 +1,6 @@
 """First-step gradient of a GRU learner fixture (tests/golden/learner_*.npz) on the kernels against the
 reference's recorded gradient, beside the torch agent-stacked fp32 path, per tensor, with the location of
-the largest kernel error (the input column, for weight_ih).  Run once per library variant
-(D2D_LIB_VARIANT=gdw0 / gdh0 with D2D_ALLOW_ABLATION=1: the fp32-MFMA weight-gradient / dh builds).
+the largest kernel error (the input column, for weight_ih).
 usage (GPU box): python3 tools/gpu/gru_learner_diag.py learner_ippo_rnn_cat_ep4 [E]"""
 import os
 import sys

@@ -1,7 +1,7 @@
 """Timing probe: the actor-only rollout policy kernel at the headline slot (64 agents x 8 channels x 65,536 envs,
 compact record) in its three modes -- sampled (training rollouts), deterministic (test()) and forced (D2D-PPO's
-epoch-start log-prob pass, the `chain` phase) -- for A/B of policy_kernels.hip builds (D2D_LIB_VARIANT).  With --save
-the log-probs of each mode go to a .pt file, so two builds' outputs can be compared offline.
+epoch-start log-prob pass, the `chain` phase).  With --save the log-probs of each mode go to a .pt file, so the
+outputs of two builds (two commits) can be compared offline.
 usage: python tools/gpu/policy_mode_probe.py [--envs 65536] [--reps 30] [--save PATH]"""
 import argparse
 import json
@@ -51,7 +51,7 @@ def main():
     pp = {k: v.data for k, v in lr.policy.params.items()}
     act_s, lp_s, _ = policy_mlp_step(pp, x, "comb", None, rng_step=3)
     forced = act_s.clone()
-    out = {"envs": a.envs, "lib_variant": os.environ.get("D2D_LIB_VARIANT", "")}
+    out = {"envs": a.envs}
     for _ in range(2):
         out.setdefault("sample_us", []).append(1e3 * timed(lambda: policy_mlp_step(pp, x, "comb", None, rng_step=3), a.reps))
         out.setdefault("forced_us", []).append(
