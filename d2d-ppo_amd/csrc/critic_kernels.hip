@@ -510,7 +510,7 @@ __global__ __launch_bounds__(256) void critic_dw1_reduce_kernel(int64_t n, int K
 
 using namespace d2d;
 
-static int critic_ht(int H) { return H <= 32 ? 2 : H <= 64 ? 4 : H <= 128 ? 8 : 0; }
+static int critic_ht(int H) { return H < 1 ? 0 : H <= 32 ? 2 : H <= 64 ? 4 : H <= 128 ? 8 : 0; }  // 0: unsupported
 // sample tiles per wave / chunks per iteration at HT = 3..4 (the XL path needs 4 / 2)
 constexpr int kCriticSt4 = 4, kCriticKch4 = 2;
 static int critic_st(int ht) { return ht <= 2 ? 4 : ht <= 4 ? kCriticSt4 : 2; }

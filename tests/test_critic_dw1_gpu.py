@@ -6,8 +6,8 @@ the same operands (the parts summed exactly; parts and states are exact bf16, so
 accumulation over up to 10^5 samples), whichever is larger.  Ragged shapes: hidden sizes whose last 16-unit
 tile is partial (20, 36, 100), state widths that are not a multiple of the column block (117 with ldx 120, 3,848),
 sample counts that are not a multiple of the 32-sample step, fewer samples than one step, and B = 0 (zeros).  The
-learner path (D2DPPO._critic_split_backward) is covered against float64 autograd by
-tests/test_learner_gpu.py::test_d2d_central_critic_split_gemm_matches_fp32."""
+forward that makes dhm (d2d_central_critic_fwd), and forward -> dW1 against float64 autograd without a learner, are
+tests/test_critic_fwd_gpu.py."""
 import pytest
 
 pytestmark = pytest.mark.gpu
