@@ -6,11 +6,14 @@ from .record import set_format
 
 
 def policy_mlp_step(actor, obs, kind, critic=None, forced=None, rng_step=0, deterministic=False, seed=0,
-                    env_base=0, actions=None, logp=None, value=None, want_value=True, want_actions=True):
+                    env_base=0, actions=None, logp=None, value=None, want_value=True, want_actions=True,
+                    rng_offset=None):
     """actor/critic: dicts of agent-stacked fp32 tensors w1 [N][H][F], b1 [N][H], w2 [N][A][H], b2 [N][A]
     (critic: A = 1).  obs [E][N][F] fp32, or the env kernel's ObsRecord of that shape.  kind 'comb' (Bernoulli, masks out) or 'chsel' (Categorical, ids out).
     want_value=False with critic weights passes value = NULL to the C ABI (valid usage: the value is skipped);
     want_actions=False with forced passes actions = NULL (only the log-probs are stored; actions returned as None).
+    Either flag holds also when the caller hands in the buffer it then omits: the buffer is not passed on.
+    rng_offset: device pointer of a uint32 word the kernel adds to rng_step (the graph replays' counter), or None.
     Returns (actions [E][N], logp [N][E], value [N][E] or None)."""
     lib = _lib.require_gpu()
     N, H, F = actor["w1"].shape
@@ -36,11 +39,12 @@ def policy_mlp_step(actor, obs, kind, critic=None, forced=None, rng_step=0, dete
     desc = _lib.MlpDesc(N, E, F, H, A, k, p(actor["w1"]), p(actor["b1"]), p(actor["w2"]), p(actor["b2"]),
                         p(critic["w1"]) if critic else None, p(critic["b1"]) if critic else None,
                         p(critic["w2"]) if critic else None, p(critic["b2"]) if critic else None, int(seed),
-                        int(env_base))
+                        int(env_base), rng_offset)
     optr = set_format(desc, obs)
     rc = lib.d2d_policy_mlp_step(desc, optr, None if forced is None else forced.contiguous().data_ptr(),
                                  int(rng_step), 1 if deterministic else 0,
                                  actions.data_ptr() if store_actions else None, logp.data_ptr(),
-                                 None if value is None else value.data_ptr(), _lib.stream_ptr())
+                                 value.data_ptr() if value is not None and want_value else None,
+                                 _lib.stream_ptr())
     _lib.check(rc, "d2d_policy_mlp_step")
     return (actions if store_actions else None), logp, (value if critic is not None and want_value else None)

@@ -75,6 +75,19 @@ def test_library_validates_arguments_without_gpu():
     # ABI 15: actions may be NULL in forced mode only
     assert lib.d2d_policy_mlp_step(ctypes.byref(md), w, None, 0, 0, None, w, None, None) == -1
     assert b"NULL" in lib.d2d_last_error()
+    # shape limits: obs_dim <= 64; hidden <= 128 with one input chunk (obs_dim + 1 <= 32), else <= 64; n_out in [1, 16]
+    def mlp(F=30, H=64, A=8, kind=0, critic=(None, None, None, None)):
+        d = _lib.MlpDesc(4, 32, F, H, A, kind, w, w, w, w, *critic, 0, 0, None, _lib.D2D_OBS_F32, 0, None)
+        return lib.d2d_policy_mlp_step(ctypes.byref(d), w, None, 0, 0, w, w, None, None)
+    for bad in (dict(F=65), dict(F=31, H=129), dict(F=32, H=65), dict(A=17), dict(A=0)):
+        assert mlp(**bad) == -2, bad                                   # D2D_EUNSUPPORTED
+        assert lib.d2d_last_error(), bad
+    assert mlp(kind=2) == -1 and b"kind" in lib.d2d_last_error()       # D2D_EINVAL
+    for missing in range(1, 4):                                        # a critic (v1) without c1, v2 or c2
+        crit = [w, w, w, w]
+        crit[missing] = None
+        assert mlp(critic=crit) == -1, missing
+        assert b"critic" in lib.d2d_last_error()
     # the record is a combinatorial-env output only
     dsc = _lib.EnvDesc(1, 4, 3, 7, 11, 0, 0, 1, 0, 0, w, w, w, w, w, None, None, w)
     st = _lib.EnvState(w, w, w, w, w, w)

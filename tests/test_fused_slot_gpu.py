@@ -19,7 +19,16 @@ def _learner(E, seed=5, H=64):
     from envs.combinatorial_env import CombinatorialEnv
     env = CombinatorialEnv(**bench.config3_params(200), n_envs=E, device="cuda:0", seed=seed)
     torch.manual_seed(3)
-    return iPPO(env, hidden_size=H, gamma=0.6, policy_lr=3e-4, value_lr=1e-3, device="cuda:0", combinatorial=True)
+    lr = iPPO(env, hidden_size=H, gamma=0.6, policy_lr=3e-4, value_lr=1e-3, device="cuda:0", combinatorial=True)
+    # init_weights leaves every bias zero; the kernels' bias paths need nonzero ones (the same for every learner
+    # built here: a fixed seed, and in place, so the agents' modules -- views of the stacked tensors -- see them)
+    g = torch.Generator().manual_seed(17)
+    with torch.no_grad():
+        for nets in (lr.policy, lr.value):
+            for name in ("b1", "b2"):
+                b = nets.params[name]
+                b.copy_((torch.rand(b.shape, generator=g) - 0.5).to(b.device))
+    return lr
 
 
 def _state(b):

@@ -21,6 +21,8 @@ import pytest
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
+from mlp_oracle import to_record  # noqa: E402  (the hand-built compact record, shared with test_policy_edges_gpu.py)
+
 
 @pytest.fixture(params=["split", "f32"])
 def policy_impl(request):
@@ -417,27 +419,6 @@ def xp_policy_check(mode, c):
     err = (lp - ref_lp).abs()
     print(f"  max err {err[well].max().item():.2e}; within 1e-5: {(err[well] <= 1e-5).float().mean().item():.5f}")
     assert bool((err[well] <= tol[well]).all()), (err[well].max().item(), (err / tol)[well].max().item())
-
-
-def to_record(obs):
-    """The compact obs record (d2dhip/record.py) of integer-valued fp32 obs [T][E][N][F]: one byte per
-    column (int8 where a column holds negatives), the bias byte 1 at column F, zeros past it."""
-    from d2dhip.record import ObsRecord
-    T, E, N, F = obs.shape
-    R = 32 * ((F + 1 + 31) // 32)
-    v = obs.round().to(torch.int32)
-    assert torch.equal(v.float(), obs.float()), "record inputs must be integers"
-    neg = (v < 0).reshape(-1, N, F).any(0)                                        # [N][F]
-    data = torch.zeros((T, E, N, R), dtype=torch.uint8)
-    data[..., :F] = (v & 0xFF).to(torch.uint8)
-    data[..., F] = 1                                                                # the bias input
-    sgn = torch.zeros((N, R // 32), dtype=torch.int64)
-    for k in range(N):
-        for c in range(F):
-            if neg[k, c]:
-                sgn[k, c // 32] |= 1 << (c % 32)
-    sgn = torch.where(sgn >= 2 ** 31, sgn - 2 ** 32, sgn).to(torch.int32)
-    return ObsRecord(data.cuda().contiguous(), F, sgn.cuda())
 
 
 @pytest.fixture(params=["f32", "record", "record-history"])

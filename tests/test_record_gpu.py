@@ -78,7 +78,13 @@ def mlp_nets(N, F, H, A, seed, critic=True):
     pol = StackedNets([Policy(F, A, H) for _ in range(N)], [F] * N, "mlp", "cuda", act="softmax")
     val = StackedNets([Value(F, H) for _ in range(N)], [F] * N, "mlp", "cuda") if critic else None
     d = lambda st: {k: v.detach().contiguous() for k, v in st.params.items()}  # noqa: E731
-    return d(pol), (d(val) if val is not None else None)
+    nets = d(pol), (d(val) if val is not None else None)
+    # init_weights leaves every bias zero; the kernels' bias paths need nonzero ones
+    g = torch.Generator().manual_seed(seed)
+    for net in nets:
+        for name in ("b1", "b2") if net is not None else ():
+            net[name] = (torch.rand(net[name].shape, generator=g) - 0.5).cuda()
+    return nets
 
 
 @pytest.mark.parametrize("case", ["c3", "het", "c16"])

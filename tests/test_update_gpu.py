@@ -18,7 +18,9 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 
-def make_nets(N, F, H, A, in_dims, seed, critic):
+def make_nets(N, F, H, A, in_dims, seed, critic, bias=False):
+    """The reference's initialisation (orthogonal, gain 2; every bias zero); bias=True: every bias uniform in +-0.5
+    from a generator seeded with `seed` (init_weights' zeros never reach the kernels' bias paths)."""
     from algorithms._core import Policy, StackedNets, Value
     torch.manual_seed(seed)
     dims = in_dims or [F] * N
@@ -26,7 +28,12 @@ def make_nets(N, F, H, A, in_dims, seed, critic):
         st = StackedNets([Value(d, H) for d in dims], dims, "mlp", "cpu")
     else:
         st = StackedNets([Policy(d, A, H) for d in dims], dims, "mlp", "cpu", act="softmax")
-    return {k: v.detach().clone() for k, v in st.params.items()}, dims
+    net = {k: v.detach().clone() for k, v in st.params.items()}
+    if bias:
+        g = torch.Generator().manual_seed(seed)
+        for name in ("b1", "b2"):
+            net[name] = torch.rand(net[name].shape, generator=g) - 0.5
+    return net, dims
 
 
 def make_obs(T, E, N, F, dims, seed, frac):
@@ -134,10 +141,29 @@ CASES = [
 @pytest.mark.parametrize("case", CASES, ids=[f"{c[0]}-N{c[1]}-T{c[2]}-E{c[3]}-F{c[4]}-H{c[5]}-A{c[6]}"
                                               f"{'-het' if c[7] else ''}{'-frac' if c[8] else ''}" for c in CASES])
 def test_actor_grad_matches_autograd(case):
+    _actor_case(case, bias=False)
+
+
+# the same with nonzero biases (b1 riding in input column F of the split kernels, b2 per action)
+BIAS_CASES = [
+    ("comb", 4, 3, 100, 30, 64, 8, None, False),
+    ("chsel", 3, 2, 70, 12, 128, 5, None, True),
+    ("comb", 3, 2, 45, 46, 32, 16, None, True),
+    ("comb", 2, 2, 33, 31, 128, 8, None, False),
+]
+
+
+@pytest.mark.parametrize("case", BIAS_CASES, ids=[f"{c[0]}-N{c[1]}-T{c[2]}-E{c[3]}-F{c[4]}-H{c[5]}-A{c[6]}"
+                                                   f"{'-frac' if c[8] else ''}" for c in BIAS_CASES])
+def test_actor_grad_matches_autograd_with_biases(case):
+    _actor_case(case, bias=True)
+
+
+def _actor_case(case, bias):
     from d2dhip.envbatch import pack_masks_torch
     from d2dhip.update import actor_grads
     kind, N, T, E, F, H, A, dims, frac = case
-    net, dims_ = make_nets(N, F, H, A, dims, seed=3, critic=False)
+    net, dims_ = make_nets(N, F, H, A, dims, seed=3, critic=False, bias=bias)
     obs = make_obs(T, E, N, F, dims_, seed=5, frac=frac)
     g = torch.Generator().manual_seed(9)
     B = T * E
@@ -181,9 +207,19 @@ def test_actor_grad_matches_autograd(case):
 @pytest.mark.parametrize("case", [c for c in CASES if c[0] == "comb"],
                          ids=lambda c: f"N{c[1]}-T{c[2]}-E{c[3]}-F{c[4]}-H{c[5]}{'-frac' if c[8] else ''}")
 def test_critic_grad_matches_autograd(case):
+    _critic_case(case, bias=False)
+
+
+@pytest.mark.parametrize("case", [c for c in BIAS_CASES if c[0] == "comb"],
+                         ids=lambda c: f"N{c[1]}-T{c[2]}-E{c[3]}-F{c[4]}-H{c[5]}{'-frac' if c[8] else ''}")
+def test_critic_grad_matches_autograd_with_biases(case):
+    _critic_case(case, bias=True)
+
+
+def _critic_case(case, bias):
     from d2dhip.update import critic_grads
     _, N, T, E, F, H, _, dims, frac = case
-    net, dims_ = make_nets(N, F, H, 1, dims, seed=4, critic=True)
+    net, dims_ = make_nets(N, F, H, 1, dims, seed=4, critic=True, bias=bias)
     obs = make_obs(T, E, N, F, dims_, seed=6, frac=frac)
     g = torch.Generator().manual_seed(2)
     R = torch.randn(N, T * E, generator=g)
