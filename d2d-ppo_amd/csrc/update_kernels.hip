@@ -29,7 +29,7 @@
 // orientations, dH) on the exact three-way bf16 split (mlp_common.h), the logits and dW2 on fp32
 // MFMA -- fp32-accurate; the weight-gradient GEMMs dW1 = dH^T X and dW2 = h^T dZ on two-way RNE
 // splits of their per-tile operands (<= 2^-17 relative per term).
-// Parity with torch autograd: tests/test_update_gpu.py (2e-5 of max|grad| vs float64).
+// Parity with torch autograd: tests/test_update_gpu.py, tests/test_update_edges_gpu.py (2e-5 of max|grad| vs float64).
 //
 // Partial sums: every wave accumulates its tiles in registers; the four waves of a workgroup
 // are summed in fixed order through LDS and written as one partial per (workgroup, agent);
@@ -167,7 +167,8 @@ __device__ __forceinline__ uint32_t relu_mask_pair(float r0, float r1) {
   const uint32_t hi = __builtin_amdgcn_perm(fbits(r1), fbits(r0), 0x07060302u);
   uint32_t m, o;
   asm("v_pk_min_u16 %0, %1, %2" : "=v"(m) : "v"(hi), "s"(0x00010001u));
-  asm("v_pk_mul_lo_u16 %0, %1, %2" : "=v"(o) : "v"(m), "s"(0x3F803F80u));
+  // (s_nop 1: the mask is an MFMA operand, see mfma_operand_pad below)
+  asm("v_pk_mul_lo_u16 %0, %1, %2\n\ts_nop 1" : "=v"(o) : "v"(m), "s"(0x3F803F80u));
   return o;
 }
 
@@ -181,6 +182,18 @@ __device__ __forceinline__ uint32_t pk_mul_lo_u16(uint32_t a, uint32_t b) {
   uint32_t o;
   asm("v_pk_mul_lo_u16 %0, %1, %2" : "=v"(o) : "v"(a), "v"(b));
   return o;
+}
+// An MFMA that reads a register as A or B needs two wait states after the VALU write of that register.  The compiler
+// pads the instructions it emits itself, but not an asm statement's: it does not know what the statement writes with,
+// and it may schedule the MFMA right behind it (ppo_actor_grad_kernel<2, 2, 1, true, true>: v_pk_mul_lo_u16, one
+// VALU, the first dW1 MFMA -- which then read the previous tile's operand dword; tests/test_update_edges_gpu.py).
+// Operand dwords made by the asm helpers above pass through this statement before the MFMA: it depends on all of them,
+// the MFMA depends on it, and its s_nop 1 is the pad.
+__device__ __forceinline__ void mfma_operand_pad(uint32_t (&v)[4]) {
+  asm("s_nop 1" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]));
+}
+__device__ __forceinline__ void mfma_operand_pad(uint32_t (&v)[4], uint32_t (&w)[4]) {
+  asm("s_nop 1" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]));
 }
 
 // high parts only (bf16-exact values)
@@ -634,7 +647,6 @@ __global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? kUpdWaves : 1) void ppo
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         bf16x8 bz1, bz2;
-        const uint32_t zz[2] = {0u, 0u};
         if constexpr (DZ1) {
           // dZ's h / m parts of samples 4g .. 4g + 3 (this half), action i, transposed from the bf16 rows
           typedef __attribute__((address_space(3))) v4i16* lds_v4i16;
@@ -643,7 +655,7 @@ __global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? kUpdWaves : 1) void ppo
           const uint2 zm = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4i16)(zr + 256)));
           const uint32_t zh2[2] = {zh.x, zh.y}, zm2[2] = {zm.x, zm.y};
           bz1 = cat(zh2, zh2);
-          bz2 = cat(zm2, zz);
+          bz2 = cat(zm2, zm2);
         } else {
           float dzn[4];
 #pragma unroll
@@ -653,7 +665,7 @@ __global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? kUpdWaves : 1) void ppo
           // 120 VALU per tile but measured 13 % slower: the fp32 MFMAs' issue cost outweighs the VALU)
           const Parts2x4 zn = split2_4(dzn);
           bz1 = cat(zn.h, zn.h);
-          bz2 = cat(zn.m, zz);
+          bz2 = cat(zn.m, zn.m);
         }
         bf16x8 bx1[QT], bx2[QT];
 #pragma unroll
@@ -720,9 +732,10 @@ __global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? kUpdWaves : 1) void ppo
               const Parts2x4 dp = split2_4(av);
               const uint2 tw = __builtin_bit_cast(uint2, th);
               const uint32_t m0 = pk_min1_u16(tw.x), m1 = pk_min1_u16(tw.y);
-              const uint32_t dh2[2] = {pk_mul_lo_u16(m0, dp.h[0]), pk_mul_lo_u16(m1, dp.h[1])};
-              const uint32_t dm2[2] = {pk_mul_lo_u16(m0, dp.m[0]), pk_mul_lo_u16(m1, dp.m[1])};
-              d_hm = cat(dh2, dm2);
+              uint32_t dhm[4] = {pk_mul_lo_u16(m0, dp.h[0]), pk_mul_lo_u16(m1, dp.h[1]),
+                                 pk_mul_lo_u16(m0, dp.m[0]), pk_mul_lo_u16(m1, dp.m[1])};
+              mfma_operand_pad(dhm);
+              d_hm = as_frag(dhm);
             } else {
               float dh[4];
 #pragma unroll
@@ -762,7 +775,7 @@ __global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? kUpdWaves : 1) void ppo
             dh[r] = hn[r] > 0.f ? acc[r] : 0.f;
             hr[r] = relu(hn[r]);
           }
-          // dW2^T += relu(HN)^T . dZ: (h_h + h_m) dz_h + h_h dz_m, k-slots = 4 samples x 2 parts
+          // dW2^T += relu(HN)^T . dZ: (h_h + h_m) (dz_h + dz_m), k-slots = 4 samples x 2 parts
           const Parts2x4 hp = split2_4(hr);
           const bf16x8 h_hm = cat(hp.h, hp.m);
           dw2[t2] = mfma_bf16(h_hm, bz2, dw2[t2]);
@@ -1402,6 +1415,7 @@ __global__ __launch_bounds__(256, (KC == 1 && HT <= 4) ? (U8 ? kCriticTWaves : k
           ah[p] = pk_mul_lo_u16(m01, DH[p]);
           am[p] = pk_mul_lo_u16(m01, DM[p]);
         }
+        mfma_operand_pad(ah, am);
         const bf16x8 Ah = as_frag(ah), Am = as_frag(am);
         // (part-outer: the QT accumulators' chains interleave)
         if constexpr (!XE) {
@@ -1630,6 +1644,18 @@ static int launch_reduce(const UpdArgs& a, float* gw1, float* gb1, float* gw2, f
   return D2D_OK;
 }
 
+// No sample (T = 0 or n_envs = 0): every sum is empty.  The outputs are zeroed directly -- d2d_ppo_workspace asks for
+// no scratch then, so there is no partial to reduce.
+static int zero_outputs(const UpdArgs& a, float* gw1, float* gb1, float* gw2, float* gb2, float* stats, hipStream_t s) {
+  const size_t N = (size_t)a.N;
+  D2D_CHECK_HIP(hipMemsetAsync(gw1, 0, sizeof(float) * N * a.H * a.F, s));
+  D2D_CHECK_HIP(hipMemsetAsync(gb1, 0, sizeof(float) * N * a.H, s));
+  D2D_CHECK_HIP(hipMemsetAsync(gw2, 0, sizeof(float) * N * a.A * a.H, s));
+  D2D_CHECK_HIP(hipMemsetAsync(gb2, 0, sizeof(float) * N * a.A, s));
+  if (stats) D2D_CHECK_HIP(hipMemsetAsync(stats, 0, sizeof(float) * N * 2, s));
+  return D2D_OK;
+}
+
 // KRES: the instantiation whose residency sizes the grid -- the record (U8) one for both input formats, so that
 // fp32 rows and the record split the tiles into the same workgroup partials and sum them in the same order (their
 // gradients are bitwise equal on bf16-exact inputs, tests/test_record_gpu.py)
@@ -1696,11 +1722,7 @@ extern "C" int d2d_ppo_actor_grad(const d2d_mlp_desc* d, int32_t T, const void* 
   a.clip_lo = 1.f - clip; a.clip_hi = 1.f + clip; a.beta = beta; a.scale = scale;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (a.N == 0) return D2D_OK;
-  if (a.n_tiles == 0) {
-    D2D_CHECK_HIP(hipMemsetAsync(workspace, 0, sizeof(float) * (size_t)a.N * a.P, s));
-    a.G = 1;
-    return launch_reduce(a, gw1, gb1, gw2, gb2, stats, s);
-  }
+  if (a.n_tiles == 0) return zero_outputs(a, gw1, gb1, gw2, gb2, stats, s);
   const int ht = (a.H + 15) / 16;
   if (a.F + 1 <= 32) {
     if (ht <= 2) launch_actor<1, 2>(a, s); else if (ht <= 4) launch_actor<1, 4>(a, s); else launch_actor<1, 8>(a, s);
@@ -1749,11 +1771,7 @@ extern "C" int d2d_ppo_critic_grad_values(const d2d_mlp_desc* d, int32_t T, cons
   a.scale = scale;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (a.N == 0) return D2D_OK;
-  if (a.n_tiles == 0) {
-    D2D_CHECK_HIP(hipMemsetAsync(workspace, 0, sizeof(float) * (size_t)a.N * a.P, s));
-    a.G = 1;
-    return launch_reduce(a, gw1, gb1, gw2, gb2, stats, s);
-  }
+  if (a.n_tiles == 0) return zero_outputs(a, gw1, gb1, gw2, gb2, stats, s);
   const int ht = (a.H + 15) / 16;
   if (a.F + 1 <= 32) {
     if (ht <= 2) launch_critic<1, 2>(a, s); else if (ht <= 4) launch_critic<1, 4>(a, s); else launch_critic<1, 8>(a, s);
