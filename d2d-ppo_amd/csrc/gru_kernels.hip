@@ -480,6 +480,21 @@ __global__ __launch_bounds__(256, 1) void gru_grad_kernel(GruArgs a) {
   const SwzOff<16 * IT> oi(g, i);  // (unused: W_ih comes from the global image)
   const SwzOff<HW> oh(g, i);
   const XSigns<IT> xsg(a.ov, k);
+  // Whether a step's inputs are all bf16-exact (three W_ih part products instead of six, chosen per step by a wave-wide
+  // ballot).  The HT = 4, IT >= 3 instances take the six products at every step instead.  With the branch, and in
+  // these instances only, the compiler keeps a gate tile's sum in a second accumulator quad and copies it back
+  // (v_accvgpr_mov_b32) where the two sides join; on the six-product side the copy is reached through two scalar
+  // branches straight after the MFMA that writes the quad, without the wait states an MFMA result needs before a
+  // VALU read (the s_nop pads are on the other side only).  It read stale accumulators: loss sums and all eight
+  // gradients up to 1e5 x the tolerance off for any window with one inexact input
+  // (tests/test_gru_edges_gpu.py::test_grads_fractional_inputs).  Without the branch there is no join
+  // and no copy.  For exact inputs the extra products add exact zeros: the same bits as before.  (The cooperative
+  // instances read exact inputs by construction and never ask.)
+  constexpr bool kSixProducts = HT == 4 && IT >= 3;
+  auto x_exact = [&](const float (&x)[IT][4]) {
+    if constexpr (kSixProducts) return false;
+    else return x_exact_step<IT>(a.ov, x);
+  };
   const size_t wave_id = (size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 4 + wave;
   // per wave: [0, L) the tile's h_j, [L, 2L) the front-padding table: h after j + 1 all-padding steps,
   // (PADC) [2L, 3L) the padding-region entry sums: ent[j] = sum of dh_j over the tiles whose BPTT stopped at j + 1
@@ -568,7 +583,7 @@ __global__ __launch_bounds__(256, 1) void gru_grad_kernel(GruArgs a) {
     f32x4 rz[2 * HT], ni[HT], nh[HT];
     const int z = opaque_zero();
     if constexpr (SPLIT)
-      gru_preact_split<HT, IT, COOP>(wih_g + z, whh_b + z, lane, x, x_exact_step<IT>(a.ov, x), h, bhn, rz, ni, nh, j == 0);
+      gru_preact_split<HT, IT, COOP>(wih_g + z, whh_b + z, lane, x, x_exact(x), h, bhn, rz, ni, nh, j == 0);
     else
       gru_preact<HT, IT, false>(wimg + z, whh_s + z, oi, oh, x, h, bhn, rz, ni, nh, g, i, j == 0);
     gru_gates<HT>(rz, ni, nh, h);
@@ -637,7 +652,7 @@ __global__ __launch_bounds__(256, 1) void gru_grad_kernel(GruArgs a) {
       f32x4 rz[2 * HT], ni[HT], nh[HT];
       const int z = opaque_zero();
       if constexpr (SPLIT)
-        gru_preact_split<HT, IT, COOP>(wih_g + z, whh_b + z, lane, x, x_exact_step<IT>(a.ov, x), h, bhn, rz, ni, nh, j == 0);
+        gru_preact_split<HT, IT, COOP>(wih_g + z, whh_b + z, lane, x, x_exact(x), h, bhn, rz, ni, nh, j == 0);
       else
         gru_preact<HT, IT, false>(wimg + z, whh_s + z, oi, oh, x, h, bhn, rz, ni, nh, g, i, j == 0);
       gru_gates<HT>(rz, ni, nh, h);
@@ -796,7 +811,7 @@ __global__ __launch_bounds__(256, 1) void gru_grad_kernel(GruArgs a) {
       f32x4 rz[2 * HT], ni[HT], nh[HT];
       const int z = opaque_zero();
       if constexpr (SPLIT)
-        gru_preact_split<HT, IT, COOP>(wih_g + z, whh_b + z, lane, x, x_exact_step<IT>(a.ov, x), hp, bhn, rz, ni, nh, j == 0);
+        gru_preact_split<HT, IT, COOP>(wih_g + z, whh_b + z, lane, x, x_exact(x), hp, bhn, rz, ni, nh, j == 0);
       else
         gru_preact<HT, IT, false>(wimg + z, whh_s + z, oi, oh, x, hp, bhn, rz, ni, nh, g, i, j == 0);
       __builtin_amdgcn_sched_barrier(0);
@@ -1655,6 +1670,7 @@ extern "C" int d2d_gru_grad(const d2d_gru_desc* d, int32_t T, const void* obs, c
     a.w_st[q] = weight_strides[q];
   }
   a.clip_lo = 1.f - clip; a.clip_hi = 1.f + clip; a.beta = beta; a.scale = scale;
+  if (a.N == 0) return D2D_OK;  // no agent, no output (and gru_grad_blocks divides by N)
   const int64_t tiles = (int64_t)T * a.env_tiles;
   a.G = gru_grad_blocks(a.N, tiles);
   const GruOff o(a.H, a.F, a.A);
@@ -1669,8 +1685,24 @@ extern "C" int d2d_gru_grad(const d2d_gru_desc* d, int32_t T, const void* obs, c
   a.himg = workspace + ws.himg;
   a.ghist = workspace + ws.ghist;
   a.gpart = workspace + ws.gpart;
-  if (a.N == 0) return D2D_OK;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (tiles == 0) {
+    // an empty batch (T = 0 or no envs): every gradient and loss sum is zero.  The workspace query answers 0
+    // floats for it, so nothing may touch `workspace` -- no image kernel, no partials, no reduce
+    const size_t H = (size_t)a.H, N = (size_t)a.N, F = (size_t)a.F, A = (size_t)a.A, f = sizeof(float);
+    D2D_CHECK_HIP(hipMemsetAsync(g_w_ih, 0, f * N * 3 * H * F, s));
+    D2D_CHECK_HIP(hipMemsetAsync(g_w_hh, 0, f * N * 3 * H * H, s));
+    D2D_CHECK_HIP(hipMemsetAsync(g_b_ih, 0, f * N * 3 * H, s));
+    D2D_CHECK_HIP(hipMemsetAsync(g_b_hh, 0, f * N * 3 * H, s));
+    D2D_CHECK_HIP(hipMemsetAsync(g_w1, 0, f * N * H * H, s));
+    D2D_CHECK_HIP(hipMemsetAsync(g_b1, 0, f * N * H, s));
+    D2D_CHECK_HIP(hipMemsetAsync(g_w2, 0, f * N * A * H, s));
+    D2D_CHECK_HIP(hipMemsetAsync(g_b2, 0, f * N * A, s));
+    if (stats) {
+      D2D_CHECK_HIP(hipMemsetAsync(stats, 0, f * N * 2, s));
+    }
+    return D2D_OK;
+  }
   {
     if (htp == 1) launch_wih_split<1>(a, itp, s);
     else if (htp == 2) launch_wih_split<2>(a, itp, s);
@@ -1681,10 +1713,7 @@ extern "C" int d2d_gru_grad(const d2d_gru_desc* d, int32_t T, const void* obs, c
     else if (htp == 2) hipLaunchKernelGGL(gru_head_image_kernel<2>, gh, dim3(256), 0, s, a.w, a.N, a.H, a.A, a.himg);
     else hipLaunchKernelGGL(gru_head_image_kernel<4>, gh, dim3(256), 0, s, a.w, a.N, a.H, a.A, a.himg);
   }
-  if (tiles == 0) {
-    D2D_CHECK_HIP(hipMemsetAsync(workspace, 0, sizeof(float) * (size_t)a.N * a.P, s));
-    a.G = 1;
-  } else {
+  {
     dim3 grid(a.N, a.G);
     if (ht <= 1) launch_grad_it<1>(a, itp, grid, s, false);
     else if (ht <= 2) launch_grad_it<2>(a, itp, grid, s, false);

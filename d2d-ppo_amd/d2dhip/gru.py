@@ -11,6 +11,26 @@ from .record import set_format
 KIND = {"sigmoid": 0, "softmax": 1, None: 2}
 
 
+_dummy = {}
+
+
+def _numel(t):
+    return t.data.numel() if hasattr(t, "obs_dim") else t.numel()
+
+
+def _ptr(t, p=None):
+    """Device pointer of tensor t (or p, the pointer already taken of it).  Only an empty tensor, which has no storage
+    (data_ptr() == 0), gets a stand-in: the C ABI refuses NULL before it looks at the sizes, and never dereferences
+    the pointers of an empty batch.  A NULL pointer of a non-empty tensor stays NULL and is refused there."""
+    p = t.data_ptr() if p is None else p
+    if p or _numel(t):
+        return p
+    dev = t.device
+    if dev not in _dummy:
+        _dummy[dev] = torch.zeros((4,), dtype=torch.float32, device=dev)
+    return _dummy[dev].data_ptr()
+
+
 def desc(params, n_envs, kind, history_len, episode_length, seed=0, env_base=0, rng_offset=None):
     """d2d_gru_desc of agent-stacked RNN params (StackedNets kind 'rnn': w_ih, w_hh, b_ih, b_hh, w1, b1, w2, b2)."""
     p = params
@@ -21,7 +41,7 @@ def desc(params, n_envs, kind, history_len, episode_length, seed=0, env_base=0, 
         if t.dtype != torch.float32 or not t.is_contiguous():
             raise ValueError("GRU params must be contiguous float32")
     d = _lib.GruDesc(N, int(n_envs), F, H, A, int(kind), int(history_len), int(episode_length),
-                     *(p[n].data_ptr() for n in ("w_ih", "w_hh", "b_ih", "b_hh", "w1", "b1", "w2", "b2")),
+                     *(_ptr(p[n]) for n in ("w_ih", "w_hh", "b_ih", "b_hh", "w1", "b1", "w2", "b2")),
                      int(seed) & 0xFFFFFFFFFFFFFFFF, int(env_base), None if rng_offset is None else rng_offset)
     return d
 
@@ -48,8 +68,8 @@ def policy(params, obs, kind, history_len, episode_length, slot0, n_slots, padde
     T, E, N, F = obs.shape
     k = KIND[kind]
     d = desc(params, E, k, history_len, episode_length, seed, env_base, rng_offset)
-    optr = set_format(d, obs)
     dev = obs.device
+    optr = _ptr(obs, set_format(d, obs))
     if out is None:
         out = torch.empty((N, n_slots * E), dtype=torch.float32, device=dev)
     act = None
@@ -66,13 +86,13 @@ def policy(params, obs, kind, history_len, episode_length, slot0, n_slots, padde
             raise ValueError("hcarry must be a float32 device tensor of d2d_gru_carry_floats elements")
         rc = lib.d2d_policy_gru_carry(ctypes.byref(d), T, optr, int(slot0), None if forced is None else forced.data_ptr(),
                                       int(rng_step) & 0xFFFFFFFF, 1 if deterministic else 0,
-                                      None if act is None else act.data_ptr(), out.data_ptr(), hcarry.data_ptr(),
+                                      None if act is None else _ptr(act), _ptr(out), hcarry.data_ptr(),
                                       1 if carry_in else 0, _lib.stream_ptr())
         _lib.check(rc, "d2d_policy_gru_carry")
         return (act, out) if k != 2 else out
     rc = lib.d2d_policy_gru(ctypes.byref(d), T, optr, int(slot0), int(n_slots), 1 if padded else 0,
                             None if forced is None else forced.data_ptr(), int(rng_step) & 0xFFFFFFFF,
-                            1 if deterministic else 0, None if act is None else act.data_ptr(), out.data_ptr(),
+                            1 if deterministic else 0, None if act is None else _ptr(act), _ptr(out),
                             _lib.stream_ptr())
     _lib.check(rc, "d2d_policy_gru")
     return (act, out) if k != 2 else out
@@ -113,18 +133,19 @@ def grads(params, obs, kind, history_len, episode_length, weight, actions=None, 
     T, E, N, F = obs.shape
     k = KIND[kind]
     d = desc(params, E, k, history_len, episode_length)
-    optr = set_format(d, obs)
     dev = obs.device
+    optr = _ptr(obs, set_format(d, obs))
     grads = grads if grads is not None else {n: torch.empty_like(v) for n, v in params.items()}
     if stats is None:
         stats = torch.empty((N, 2), dtype=torch.float32, device=dev)
-    scale = 1.0 / (T * E) if scale is None else scale
+    if scale is None:
+        scale = 1.0 / (T * E) if T * E else 0.0    # an empty batch: every gradient and loss sum is zero
     ws = _ws.get(lib.d2d_gru_grad_workspace(ctypes.byref(d), T), dev)
     lo_st = _arr(_strides3(logp_old, T, E, N)) if logp_old is not None else None
-    rc = lib.d2d_gru_grad(ctypes.byref(d), T, optr, None if actions is None else actions.data_ptr(),
-                          None if logp_old is None else logp_old.data_ptr(), lo_st, weight.data_ptr(),
+    rc = lib.d2d_gru_grad(ctypes.byref(d), T, optr, None if actions is None else _ptr(actions),
+                          None if logp_old is None else _ptr(logp_old), lo_st, _ptr(weight),
                           _arr(_strides3(weight, T, E, N)), float(clip), float(beta), float(scale),
-                          *(grads[n].data_ptr() for n in ("w_ih", "w_hh", "b_ih", "b_hh", "w1", "b1", "w2", "b2")),
-                          stats.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr())
+                          *(_ptr(grads[n]) for n in ("w_ih", "w_hh", "b_ih", "b_hh", "w1", "b1", "w2", "b2")),
+                          _ptr(stats), ws.data_ptr(), ws.numel(), _lib.stream_ptr())
     _lib.check(rc, "d2d_gru_grad")
     return grads, stats

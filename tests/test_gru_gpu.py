@@ -21,6 +21,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
+from gru_oracle import gru_ref, head, make_obs, ref_loss_grads, window_groups  # noqa: E402,F401  (shared with test_gru_edges_gpu.py)
 from mlp_oracle import to_record  # noqa: E402  (the hand-built compact record, shared with test_policy_edges_gpu.py)
 
 
@@ -46,37 +47,6 @@ def make_net(N, F, H, A, seed, in_dims=None):
     p["w_ih"] *= 2.0
     p["w_hh"] *= 2.0
     return p, dims
-
-
-def make_obs(T, E, N, F, dims, seed, frac=False):
-    g = torch.Generator().manual_seed(seed)
-    obs = torch.zeros(T, E, N, F)
-    D = max(1, F // 3)
-    obs[..., :D] = torch.randint(0, 4, (T, E, N, D), generator=g).float()
-    obs[..., D:] = torch.randint(-1, 2, (T, E, N, F - D), generator=g).float()
-    if frac:
-        obs += torch.rand(obs.shape, generator=g) * 0.3
-    for k, d in enumerate(dims):
-        obs[:, :, k, d:] = 0
-    return obs
-
-
-def gru_ref(p, obs, ep_len, L, padded, kind, dtype=torch.float64):
-    """torch reference: outputs [N][T][E][A] (probs, or values [N][T][E]) of every slot's window."""
-    from algorithms._core import gru_window
-    T, E, N, F = obs.shape
-    q = {k: v.to(dtype) for k, v in p.items()}
-    outs = []
-    for t in range(T):
-        S = min(t % ep_len + 1, L)
-        win = obs[t - S + 1: t + 1].to(dtype).permute(2, 1, 0, 3)                # [N][E][S][F]
-        if padded and S < L:
-            win = torch.cat([torch.zeros(N, E, L - S, F, dtype=dtype), win], 2)
-        h = gru_window(win, q["w_ih"], q["w_hh"], q["b_ih"], q["b_hh"])          # [N][E][H]
-        y = torch.relu(torch.baddbmm(q["b1"].unsqueeze(1), h, q["w1"].transpose(1, 2)))
-        z = torch.baddbmm(q["b2"].unsqueeze(1), y, q["w2"].transpose(1, 2))        # [N][E][A]
-        outs.append(torch.sigmoid(z) if kind == "sigmoid" else torch.softmax(z, -1) if kind == "softmax" else z[..., 0])
-    return torch.stack(outs, 1)
 
 
 CASES = [
@@ -155,37 +125,6 @@ def test_gru_policy_matches_torch(case, padded, policy_impl):
     a_s, lp_s = gru.policy(pd, od, kind, L, ep, 0, T, padded=padded, rng_step=5, seed=11)
     _, lp_f = gru.policy(pd, od, kind, L, ep, 0, T, padded=padded, forced=a_s)
     torch.testing.assert_close(lp_f, lp_s, rtol=0, atol=0)
-
-
-def ref_loss_grads(p, obs, ep, L, kind, acts, logp_old, W, clip, beta, dtype):
-    """autograd of the per-agent losses summed over agents (each agent's gradient is its own)."""
-    from torch.distributions import Bernoulli, Categorical
-    q = {k: v.to(dtype).clone().requires_grad_() for k, v in p.items()}
-    out = gru_ref(q, obs, ep, L, True, kind, dtype)                            # [N][T][E](A)
-    N = out.shape[0]
-    if kind is None:
-        loss = ((out - W.to(dtype)) ** 2).reshape(N, -1).mean(1)
-        sq = ((out - W.to(dtype)) ** 2).reshape(N, -1).sum(1)
-        stats = torch.stack([sq, torch.zeros_like(sq)], 1)
-    else:
-        if kind == "sigmoid":
-            d = Bernoulli(probs=out, validate_args=False)
-            logp = d.log_prob(acts.to(dtype)).mean(-1)
-            ent = d.entropy().mean(-1)
-        else:
-            d = Categorical(probs=out, validate_args=False)
-            logp = d.log_prob(acts)
-            ent = d.entropy()
-        ratio = torch.exp(logp - logp_old.to(dtype))
-        Wd = W.to(dtype)
-        s = torch.min(ratio * Wd, torch.clamp(ratio, 1 - clip, 1 + clip) * Wd)
-        loss = -s.reshape(N, -1).mean(1) - beta * ent.reshape(N, -1).mean(1)
-        stats = torch.stack([s.reshape(N, -1).sum(1), ent.reshape(N, -1).sum(1)], 1)
-    loss.sum().backward()
-    # (history_len 1: h0 = 0 is the window's only hidden input, so W_hh never enters the graph -- its gradient
-    # is exactly zero)
-    return ({k: v.grad if v.grad is not None else torch.zeros_like(v) for k, v in q.items()}, stats.detach(),
-            out.detach())
 
 
 GRAD_CASES = [
@@ -299,37 +238,6 @@ def test_gru_grads_bitwise_reproducible_and_large(fmt):
 # xp_load.py:78-89's configuration: hidden_size = 64, history_len = n_agents = 64 (the bench's GRU leg),
 # 64 agents, 30 inputs (14 + 2 * 8), episode_length 200: T = 200 slots (a full episode) of E = 4 envs.
 XP = dict(N=64, F=30, H=64, A=8, L=64, ep=200, T=200, E=4)
-
-
-def window_groups(obs, ep, L, padded):
-    """The windows of every slot, grouped by length: [(slots, x [N][len(slots) * E][S][F])].  Training
-    windows are front-zero-padded to L (one group, ippo.py:390-403); rollout windows hold the last
-    S = min(p + 1, L) obs of the episode (ippo.py:302-304), one group per S."""
-    T, E, N, F = obs.shape
-    pos = torch.arange(T) % ep
-    S_of = torch.clamp(pos + 1, max=L)
-    groups = []
-    for S in ([L] if padded else sorted(set(S_of.tolist()))):
-        slots = torch.arange(T) if padded else torch.nonzero(S_of == S)[:, 0]
-        xs = []
-        for t in slots.tolist():
-            s = min(int(pos[t]) + 1, L)
-            w = obs[t - s + 1: t + 1]                                                 # [s][E][N][F]
-            if s < S:
-                w = torch.cat([torch.zeros(S - s, E, N, F, dtype=obs.dtype, device=obs.device), w], 0)
-            xs.append(w)
-        x = torch.stack(xs, 0).permute(3, 0, 2, 1, 4).reshape(N, len(xs) * E, S, F)   # [N][slots*E][S][F]
-        groups.append((slots, x))
-    return groups
-
-
-def head(q, h, kind, flip=None):
-    """The RNN head; flip (bool [N][B][H]) inverts the relu mask of those (sample, unit) pairs (their
-    pre-activations are within fp32 rounding of 0, so y ~ 0 either way and only the gradient's mask changes)."""
-    pre = torch.baddbmm(q["b1"].unsqueeze(1), h, q["w1"].transpose(1, 2))
-    y = torch.relu(pre) if flip is None else pre * ((pre > 0) ^ flip).to(pre.dtype)
-    z = torch.baddbmm(q["b2"].unsqueeze(1), y, q["w2"].transpose(1, 2))
-    return torch.sigmoid(z) if kind == "sigmoid" else torch.softmax(z, -1) if kind == "softmax" else z[..., 0]
 
 
 def gru_ref_grouped(p, obs, ep, L, padded, kind, dtype, chunk=None):
