@@ -336,6 +336,10 @@ __device__ __forceinline__ void flush_bf16(uint16_t* __restrict__ dst, const flo
 // Markov channel, ACK vector in {-1, 0, 1}.
 //   CT    : compile-time channel count (0 = runtime a.C)
 //   RESET : reset instead of step (combinatorial_env.py:61-114)
+//   PACKED: the packed per-agent state (d2d_env_packed_state): a.buf holds the rows with the channel mask in
+//           the top sizeof(MaskT) bytes of the last word (max_deadline + mask bytes <= 4 DW, checked by the
+//           host), a.recv one counter word per agent, received in the low and discarded in the high half;
+//           a.chan and a.disc are not touched.  Only the state load and the state store differ.
 // LDS: [cnt_words][per-wave obs slots: 64*F floats each][state]
 //   N <= 64 : state staged per wave (the wave's envs), flushed by the wave;
 //   N  > 64 : state of the block's single env staged per block.
@@ -344,7 +348,7 @@ __device__ __forceinline__ void flush_bf16(uint16_t* __restrict__ dst, const flo
 // (bidx = blockIdx.x); the fused env + policy slot (comb_policy_fused_kernel) runs it for the consecutive
 // env groups of its slice and passes lrec, an LDS image of the slice's records (agent k's row of env e at
 // lrec[k * lstride + 2 (e - lenv0)], two 16-byte words) that the slot's policy then reads instead of HBM.
-template <typename MaskT, int DW, bool LARGE, int CT, bool RESET>
+template <typename MaskT, int DW, bool LARGE, int CT, bool RESET, bool PACKED = false>
 __device__ __forceinline__ void comb_step(const EnvArgs a, float* lds, int bidx, uint4* lrec, int lstride, int lenv0) {
   const Lane L = lane_geometry<LARGE>(a, bidx);
   const int N = a.N, F = a.F;
@@ -360,6 +364,9 @@ __device__ __forceinline__ void comb_step(const EnvArgs a, float* lds, int bidx,
   const size_t row = (size_t)L.env * N + L.k;
   const uint64_t genv = a.env_base + (uint64_t)L.env;
   const uint32_t cmask = (C >= 32) ? 0xFFFFFFFFu : ((1u << C) - 1u);
+  // PACKED: the mask's place in the last row word
+  constexpr int kMaskShift = 32 - 8 * (int)sizeof(MaskT);
+  constexpr uint32_t kRowKeep = sizeof(MaskT) >= 4 ? 0u : ((1u << (kMaskShift & 31)) - 1u);
 
   Row<DW> b;
 #pragma unroll
@@ -370,10 +377,20 @@ __device__ __forceinline__ void comb_step(const EnvArgs a, float* lds, int bidx,
     ag = a.agents[L.k];
     if (!RESET) {
       load_row<DW>(b, a.buf + row * DW);
-      h_pre = (uint32_t)reinterpret_cast<const MaskT*>(a.chan)[row] & cmask;
       act = (uint32_t)reinterpret_cast<const MaskT*>(a.actions)[row] & cmask;
-      rc = a.recv[row];
-      dc = a.disc[row];
+      if constexpr (PACKED) {
+        // the mask out of the top bytes of the last word; those bytes are zero in the register row, as
+        // row_any, the record's word-level build, row_byte and the state output expect
+        h_pre = (b.w[DW - 1] >> kMaskShift) & cmask;
+        b.w[DW - 1] &= kRowKeep;
+        const uint32_t cw = a.recv[row];
+        rc = cw & 0xFFFFu;
+        dc = cw >> 16;
+      } else {
+        h_pre = (uint32_t)reinterpret_cast<const MaskT*>(a.chan)[row] & cmask;
+        rc = a.recv[row];
+        dc = a.disc[row];
+      }
     }
   }
   if (LARGE) {
@@ -458,10 +475,17 @@ __device__ __forceinline__ void comb_step(const EnvArgs a, float* lds, int bidx,
   if (RESET) dc = 0;
   // ---- state update
   if (L.active) {
-    store_row<DW>(b, a.buf + row * DW);
-    reinterpret_cast<MaskT*>(a.chan)[row] = (MaskT)h_new;
-    a.recv[row] = rc;
-    a.disc[row] = dc;
+    if constexpr (PACKED) {
+      Row<DW> o = b;
+      o.w[DW - 1] |= h_new << kMaskShift;
+      store_row<DW>(o, a.buf + row * DW);
+      a.recv[row] = rc | (dc << 16);  // both below 65,536 (the caller's bound, d2d_env_step_packed)
+    } else {
+      store_row<DW>(b, a.buf + row * DW);
+      reinterpret_cast<MaskT*>(a.chan)[row] = (MaskT)h_new;
+      a.recv[row] = rc;
+      a.disc[row] = dc;
+    }
     if (!RESET) {
       if (a.success) a.success[row] = succ ? 1 : 0;
       if (L.k == 0) {
@@ -629,10 +653,37 @@ __device__ __forceinline__ void comb_step(const EnvArgs a, float* lds, int bidx,
   }
 }
 
-template <typename MaskT, int DW, bool LARGE, int CT, bool RESET>
+template <typename MaskT, int DW, bool LARGE, int CT, bool RESET, bool PACKED = false>
 __global__ __launch_bounds__(kMaxAgents) __attribute__((amdgpu_waves_per_eu(kCombWavesPerEu))) void comb_kernel(EnvArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  comb_step<MaskT, DW, LARGE, CT, RESET>(a, lds, blockIdx.x, nullptr, 0, 0);
+  comb_step<MaskT, DW, LARGE, CT, RESET, PACKED>(a, lds, blockIdx.x, nullptr, 0, 0);
+}
+
+// =====================================================================
+// Unpacked <-> packed per-agent state of the combinatorial env (uint8 masks), one lane per agent row:
+// d2d_env_state_pack / d2d_env_state_unpack, for reading the public tensors and for the few native paths
+// that stay unpacked.  Packing truncates the counters to 16 bits (the caller's bound).
+// =====================================================================
+template <int DW, bool PACK>
+__global__ __launch_bounds__(256) void comb_state_repack_kernel(int64_t n, uint32_t* buf, uint8_t* chan, uint32_t* recv,
+                                                                uint32_t* disc, uint32_t* rows, uint32_t* counters) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  Row<DW> b;
+  if (PACK) {
+    load_row<DW>(b, buf + i * DW);
+    b.w[DW - 1] = (b.w[DW - 1] & 0x00FFFFFFu) | ((uint32_t)chan[i] << 24);
+    store_row<DW>(b, rows + i * DW);
+    counters[i] = (recv[i] & 0xFFFFu) | (disc[i] << 16);
+  } else {
+    load_row<DW>(b, rows + i * DW);
+    chan[i] = (uint8_t)(b.w[DW - 1] >> 24);
+    b.w[DW - 1] &= 0x00FFFFFFu;
+    store_row<DW>(b, buf + i * DW);
+    const uint32_t cw = counters[i];
+    recv[i] = cw & 0xFFFFu;
+    disc[i] = cw >> 16;
+  }
 }
 
 // =====================================================================
@@ -1183,14 +1234,24 @@ int launch(K kernel, const EnvArgs& a, int block, hipStream_t s, int kind) {
   return D2D_OK;
 }
 
-template <typename MaskT, int DW, int CT, bool RESET>
+template <typename MaskT, int DW, int CT, bool RESET, bool PACKED = false>
 int dispatch_comb_ct(const EnvArgs& a, int block, hipStream_t s) {
-  if (a.N > kWave) return launch(comb_kernel<MaskT, DW, true, CT, RESET>, a, block, s, D2D_ENV_COMBINATORIAL);
-  return launch(comb_kernel<MaskT, DW, false, CT, RESET>, a, block, s, D2D_ENV_COMBINATORIAL);
+  if (a.N > kWave) return launch(comb_kernel<MaskT, DW, true, CT, RESET, PACKED>, a, block, s, D2D_ENV_COMBINATORIAL);
+  return launch(comb_kernel<MaskT, DW, false, CT, RESET, PACKED>, a, block, s, D2D_ENV_COMBINATORIAL);
+}
+
+// the packed state: C <= 8 (uint8 masks) only, see packed_eligible
+template <int DW>
+int dispatch_comb_packed(const EnvArgs& a, int block, hipStream_t s) {
+  if (a.reset) return dispatch_comb_ct<uint8_t, DW, 0, true, true>(a, block, s);
+  if (a.C == 8) return dispatch_comb_ct<uint8_t, DW, 8, false, true>(a, block, s);
+  if (a.C == 4) return dispatch_comb_ct<uint8_t, DW, 4, false, true>(a, block, s);
+  return dispatch_comb_ct<uint8_t, DW, 0, false, true>(a, block, s);
 }
 
 template <int DW>
-int dispatch_comb(const EnvArgs& a, int block, hipStream_t s) {
+int dispatch_comb(const EnvArgs& a, int block, hipStream_t s, bool packed) {
+  if (packed) return dispatch_comb_packed<DW>(a, block, s);
   const int C = a.C;
   if (a.reset) {
     if (C <= 8) return dispatch_comb_ct<uint8_t, DW, 0, true>(a, block, s);
@@ -1206,7 +1267,7 @@ int dispatch_comb(const EnvArgs& a, int block, hipStream_t s) {
 }
 
 template <int DW>
-int dispatch_dw(const EnvArgs& a, int block, int kind, hipStream_t s) {
+int dispatch_dw(const EnvArgs& a, int block, int kind, hipStream_t s, bool packed) {
   if (kind == D2D_ENV_SINGLE) {
     if (a.N > kWave) return launch(single_kernel<DW, true>, a, block, s, kind);
     return launch(single_kernel<DW, false>, a, block, s, kind);
@@ -1215,20 +1276,45 @@ int dispatch_dw(const EnvArgs& a, int block, int kind, hipStream_t s) {
     if (a.N > kWave) return launch(chsel_kernel<DW, true>, a, block, s, kind);
     return launch(chsel_kernel<DW, false>, a, block, s, kind);
   }
-  return dispatch_comb<DW>(a, block, s);
+  return dispatch_comb<DW>(a, block, s, packed);
+}
+
+// The packed state exists for the combinatorial env where the row has room for the mask:
+// max_deadline + d2d_mask_bytes(C) <= 4 * d2d_buffer_words(max_deadline).  C > 8 (uint16 / uint32 masks)
+// stays unpacked: those instantiations were left out for compile time and binary size.
+int packed_eligible(const d2d_env_desc* d) {
+  if (d->env_kind != D2D_ENV_COMBINATORIAL) {
+    d2d_set_error("the packed state exists for the combinatorial env only"); return D2D_EUNSUPPORTED;
+  }
+  if (d->n_channels > 8) {
+    d2d_set_error("the packed state is built for n_channels <= 8 (uint8 masks), got %d", d->n_channels); return D2D_EUNSUPPORTED;
+  }
+  if (d->max_deadline + 1 > 4 * buffer_words(d->max_deadline)) {
+    d2d_set_error("the packed state needs max_deadline + mask bytes <= 4 * buffer words: max_deadline=%d fills its %d-byte row",
+                  d->max_deadline, 4 * buffer_words(d->max_deadline));
+    return D2D_EUNSUPPORTED;
+  }
+  return D2D_OK;
 }
 
 // the kernel arguments of one reset / step (everything but the launch geometry)
-int env_args(const d2d_env_desc* d, const d2d_env_state* st, const void* actions, const d2d_env_replay* rp,
-             const d2d_env_out* out, int reset, int t, uint32_t rng_step, EnvArgs& a) {
+// st: the unpacked state, or (pst) the packed one
+int env_args(const d2d_env_desc* d, const d2d_env_state* st, const d2d_env_packed_state* pst, bool packed,
+             const void* actions, const d2d_env_replay* rp, const d2d_env_out* out, int reset, int t, uint32_t rng_step,
+             EnvArgs& a) {
   int rc = check_desc(d);
   if (rc) return rc;
-  if (!st || !st->buffers || !st->channels || !st->received || !st->discarded) {
-    d2d_set_error("state buffers must be non-NULL"); return D2D_EINVAL;
-  }
   const bool comb = d->env_kind == D2D_ENV_COMBINATORIAL;
-  if (!comb && (!st->sel_quality || !st->sel_count)) {
-    d2d_set_error("chsel / single need sel_quality / sel_count"); return D2D_EINVAL;
+  if (packed) {
+    if (!pst || !pst->rows || !pst->counters) { d2d_set_error("packed state buffers must be non-NULL"); return D2D_EINVAL; }
+    if ((rc = packed_eligible(d))) return rc;
+  } else {
+    if (!st || !st->buffers || !st->channels || !st->received || !st->discarded) {
+      d2d_set_error("state buffers must be non-NULL"); return D2D_EINVAL;
+    }
+    if (!comb && (!st->sel_quality || !st->sel_count)) {
+      d2d_set_error("chsel / single need sel_quality / sel_count"); return D2D_EINVAL;
+    }
   }
   if (!reset && !actions) { d2d_set_error("actions is NULL"); return D2D_EINVAL; }
   memset(&a, 0, sizeof(a));
@@ -1236,8 +1322,13 @@ int env_args(const d2d_env_desc* d, const d2d_env_state* st, const void* actions
   a.S = d->state_dim; a.state_stride = d->state_stride; a.reset = reset; a.rng_step = rng_step;
   a.env_base = d->env_base; a.seed = d->seed; a.agents = d->agents; a.flip_thr = d->flip_thr;
   a.pois_cdf = d->poisson_cdf;
-  a.buf = st->buffers; a.chan = st->channels; a.recv = st->received; a.disc = st->discarded;
-  a.selq = st->sel_quality; a.seln = st->sel_count; a.actions = actions;
+  if (packed) {
+    a.buf = pst->rows; a.recv = pst->counters;
+  } else {
+    a.buf = st->buffers; a.chan = st->channels; a.recv = st->received; a.disc = st->discarded;
+    a.selq = st->sel_quality; a.seln = st->sel_count;
+  }
+  a.actions = actions;
   if (rp) { a.flips = rp->flips; a.arrivals = rp->arrivals; }
   a.gather = d->gather;
   a.rng_off = d->rng_offset;
@@ -1264,10 +1355,11 @@ int env_args(const d2d_env_desc* d, const d2d_env_state* st, const void* actions
   return D2D_OK;
 }
 
-int run_env(const d2d_env_desc* d, const d2d_env_state* st, const void* actions, const d2d_env_replay* rp,
-            const d2d_env_out* out, int reset, int t, uint32_t rng_step, void* stream) {
+int run_env(const d2d_env_desc* d, const d2d_env_state* st, const d2d_env_packed_state* pst, bool packed,
+            const void* actions, const d2d_env_replay* rp, const d2d_env_out* out, int reset, int t, uint32_t rng_step,
+            void* stream) {
   EnvArgs a;
-  if (const int rc = env_args(d, st, actions, rp, out, reset, t, rng_step, a)) return rc;
+  if (const int rc = env_args(d, st, pst, packed, actions, rp, out, reset, t, rng_step, a)) return rc;
   const int kind = d->env_kind;
   const bool comb = kind == D2D_ENV_COMBINATORIAL;
   const bool large = a.N > kWave;
@@ -1291,11 +1383,11 @@ int run_env(const d2d_env_desc* d, const d2d_env_state* st, const void* actions,
   }
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   switch (buffer_words(a.D)) {
-    case 1: return dispatch_dw<1>(a, block, kind, s);
-    case 2: return dispatch_dw<2>(a, block, kind, s);
-    case 3: return dispatch_dw<3>(a, block, kind, s);
-    case 4: return dispatch_dw<4>(a, block, kind, s);
-    default: return dispatch_dw<8>(a, block, kind, s);
+    case 1: return dispatch_dw<1>(a, block, kind, s, packed);
+    case 2: return dispatch_dw<2>(a, block, kind, s, packed);
+    case 3: return dispatch_dw<3>(a, block, kind, s, packed);
+    case 4: return dispatch_dw<4>(a, block, kind, s, packed);
+    default: return dispatch_dw<8>(a, block, kind, s, packed);
   }
 }
 
@@ -1404,13 +1496,63 @@ extern "C" int d2d_mask_bytes(int32_t n_channels) { return n_channels <= 8 ? 1 :
 
 extern "C" int d2d_env_reset(const d2d_env_desc* desc, const d2d_env_state* st, const d2d_env_replay* replay,
                              const d2d_env_out* out, uint32_t rng_step, void* stream) {
-  return run_env(desc, st, nullptr, replay, out, 1, 0, rng_step, stream);
+  return run_env(desc, st, nullptr, false, nullptr, replay, out, 1, 0, rng_step, stream);
 }
 
 extern "C" int d2d_env_step(const d2d_env_desc* desc, const d2d_env_state* st, const void* actions,
                             const d2d_env_replay* replay, const d2d_env_out* out, int32_t timestep, uint32_t rng_step,
                             void* stream) {
-  return run_env(desc, st, actions, replay, out, 0, timestep, rng_step, stream);
+  return run_env(desc, st, nullptr, false, actions, replay, out, 0, timestep, rng_step, stream);
+}
+
+extern "C" int d2d_env_reset_packed(const d2d_env_desc* desc, const d2d_env_packed_state* st,
+                                    const d2d_env_replay* replay, const d2d_env_out* out, uint32_t rng_step,
+                                    void* stream) {
+  return run_env(desc, nullptr, st, true, nullptr, replay, out, 1, 0, rng_step, stream);
+}
+
+extern "C" int d2d_env_step_packed(const d2d_env_desc* desc, const d2d_env_packed_state* st, const void* actions,
+                                   const d2d_env_replay* replay, const d2d_env_out* out, int32_t timestep,
+                                   uint32_t rng_step, void* stream) {
+  return run_env(desc, nullptr, st, true, actions, replay, out, 0, timestep, rng_step, stream);
+}
+
+namespace {
+
+template <bool PACK>
+int repack(const d2d_env_desc* d, const d2d_env_state* u, const d2d_env_packed_state* p, void* stream) {
+  int rc = check_desc(d);
+  if (rc) return rc;
+  if (!u || !u->buffers || !u->channels || !u->received || !u->discarded || !p || !p->rows || !p->counters) {
+    d2d_set_error("state buffers (unpacked and packed) must be non-NULL"); return D2D_EINVAL;
+  }
+  if ((rc = packed_eligible(d))) return rc;
+  const int64_t n = (int64_t)d->n_envs * d->n_agents;
+  if (n == 0) return D2D_OK;
+  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  uint8_t* chan = reinterpret_cast<uint8_t*>(u->channels);
+  switch (buffer_words(d->max_deadline)) {
+    case 1: hipLaunchKernelGGL((comb_state_repack_kernel<1, PACK>), grid, block, 0, s, n, u->buffers, chan, u->received, u->discarded, p->rows, p->counters); break;
+    case 2: hipLaunchKernelGGL((comb_state_repack_kernel<2, PACK>), grid, block, 0, s, n, u->buffers, chan, u->received, u->discarded, p->rows, p->counters); break;
+    case 3: hipLaunchKernelGGL((comb_state_repack_kernel<3, PACK>), grid, block, 0, s, n, u->buffers, chan, u->received, u->discarded, p->rows, p->counters); break;
+    case 4: hipLaunchKernelGGL((comb_state_repack_kernel<4, PACK>), grid, block, 0, s, n, u->buffers, chan, u->received, u->discarded, p->rows, p->counters); break;
+    default: hipLaunchKernelGGL((comb_state_repack_kernel<8, PACK>), grid, block, 0, s, n, u->buffers, chan, u->received, u->discarded, p->rows, p->counters); break;
+  }
+  D2D_CHECK_HIP(hipGetLastError());
+  return D2D_OK;
+}
+
+}  // namespace
+
+extern "C" int d2d_env_state_pack(const d2d_env_desc* desc, const d2d_env_state* src, const d2d_env_packed_state* dst,
+                                  void* stream) {
+  return repack<true>(desc, src, dst, stream);
+}
+
+extern "C" int d2d_env_state_unpack(const d2d_env_desc* desc, const d2d_env_packed_state* src, const d2d_env_state* dst,
+                                    void* stream) {
+  return repack<false>(desc, dst, src, stream);
 }
 
 extern "C" int d2d_comb_policy_fused_step(const d2d_env_desc* desc, const d2d_env_state* st, const void* actions,
@@ -1418,7 +1560,7 @@ extern "C" int d2d_comb_policy_fused_step(const d2d_env_desc* desc, const d2d_en
                                           const d2d_mlp_desc* policy, uint32_t policy_rng_step, int32_t deterministic,
                                           void* actions_out, float* logp_out, void* stream) {
   EnvArgs e;
-  if (const int rc = env_args(desc, st, actions, nullptr, out, 0, timestep, env_rng_step, e)) return rc;
+  if (const int rc = env_args(desc, st, nullptr, false, actions, nullptr, out, 0, timestep, env_rng_step, e)) return rc;
   if (desc->env_kind != D2D_ENV_COMBINATORIAL || e.N != 64 || e.C != 8 || e.rec_bytes != 32) {
     d2d_set_error("the combinatorial env with 64 agents, 8 channels and a 32-byte record only");
     return D2D_EUNSUPPORTED;

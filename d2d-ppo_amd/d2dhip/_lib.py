@@ -59,6 +59,12 @@ class EnvState(ctypes.Structure):
                 ("sel_count", _p)]
 
 
+class EnvPackedState(ctypes.Structure):
+    """d2d_env_packed_state: rows [E][N][DW] with the channel mask in the top byte of the last word, and one
+    counter word per agent (received | discarded << 16)."""
+    _fields_ = [("rows", _p), ("counters", _p)]
+
+
 class EnvOut(ctypes.Structure):
     _fields_ = [("obs", _p), ("state", _p), ("reward", _p), ("ack", _p), ("success", _p), ("obs_record", _p),
                 ("state_bf16", _p), ("state_bf16_ld", ctypes.c_int64)]
@@ -108,6 +114,15 @@ _SIGS = {
                                       ctypes.POINTER(EnvOut), ctypes.c_uint32, _p]),
     "d2d_env_step": (ctypes.c_int, [ctypes.POINTER(EnvDesc), ctypes.POINTER(EnvState), _p, ctypes.POINTER(EnvReplay),
                                      ctypes.POINTER(EnvOut), ctypes.c_int32, ctypes.c_uint32, _p]),
+    "d2d_env_reset_packed": (ctypes.c_int, [ctypes.POINTER(EnvDesc), ctypes.POINTER(EnvPackedState),
+                                             ctypes.POINTER(EnvReplay), ctypes.POINTER(EnvOut), ctypes.c_uint32, _p]),
+    "d2d_env_step_packed": (ctypes.c_int, [ctypes.POINTER(EnvDesc), ctypes.POINTER(EnvPackedState), _p,
+                                            ctypes.POINTER(EnvReplay), ctypes.POINTER(EnvOut), ctypes.c_int32,
+                                            ctypes.c_uint32, _p]),
+    "d2d_env_state_pack": (ctypes.c_int, [ctypes.POINTER(EnvDesc), ctypes.POINTER(EnvState),
+                                           ctypes.POINTER(EnvPackedState), _p]),
+    "d2d_env_state_unpack": (ctypes.c_int, [ctypes.POINTER(EnvDesc), ctypes.POINTER(EnvPackedState),
+                                             ctypes.POINTER(EnvState), _p]),
     "d2d_sample_actions": (ctypes.c_int, [ctypes.POINTER(EnvDesc), _p, ctypes.c_uint64, ctypes.c_uint32, _p]),
     "d2d_mask_bytes": (ctypes.c_int, [ctypes.c_int32]),
     "d2d_env_single_gather_map": (ctypes.c_int, [ctypes.c_int32, _p, _p, _p, ctypes.c_int32, _p, ctypes.c_int64]),

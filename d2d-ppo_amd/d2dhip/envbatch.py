@@ -4,6 +4,12 @@ All state lives in HBM (torch tensors used as plain allocations); reset/step
 are single kernel launches on the current torch stream, with no host
 synchronisation — the learners and the benchmark chain them freely and the
 whole rollout can be captured in a HIP graph.
+
+Packed state (combinatorial env): where the buffer row has room for the channel mask
+(`packed_eligible`), the state the kernels step is the packed pair `_rows` / `_counters`
+(d2d_env_packed_state), 10 bytes less per agent-step than the four unpacked tensors.  `buffers`,
+`channels`, `received` and `discarded` are then read-only VIEWS of the state, refreshed by one
+d2d_env_state_unpack launch when stale: writing into them does not change the env.
 """
 import numpy as np
 import torch
@@ -16,9 +22,22 @@ _KIND_ID = {COMB: _lib.D2D_ENV_COMBINATORIAL, "chsel": _lib.D2D_ENV_CHANNEL_SELE
 
 _MASK_DTYPE = {1: torch.uint8, 2: torch.int16, 4: torch.int32}
 
+# both packed counters (16 bits each) stay at or below this
+_COUNTER_MAX = 65535
+
+
+def packed_eligible(spec):
+    """The packed state's eligibility, as the library checks it (d2d_env_reset_packed): the combinatorial env
+    with room for the mask in the row, max_deadline + mask bytes <= 4 * buffer words, and uint8 masks (C <= 8)."""
+    return spec.kind == COMB and spec.C <= 8 and spec.D + spec.mask_bytes <= 4 * spec.DW
+
 
 class EnvBatch:
-    def __init__(self, spec: EnvSpec, n_envs, device=None, seed=0, env_base=0):
+    def __init__(self, spec: EnvSpec, n_envs, device=None, seed=0, env_base=0, packed=None):
+        """packed: None = the packed state wherever the spec is eligible; False = the unpacked state and
+        kernels (the comparison path of the tests and the A/B measurement)."""
+        if packed not in (None, False):
+            raise ValueError("packed: None (packed where eligible) or False (unpacked)")
         self.lib = _lib.require_gpu()
         self.spec = spec
         self.E = int(n_envs)
@@ -35,22 +54,35 @@ class EnvBatch:
         self._kinds_host = np.ascontiguousarray(self.kinds, dtype=np.uint8)
         self._period_host = np.ascontiguousarray(spec.period, dtype=np.float64)
         self._offset_host = np.ascontiguousarray(spec.offsets, dtype=np.float64)
-        # env state
-        self.buffers = torch.zeros((E, s.N, s.DW), dtype=torch.int32, device=dev)
+        # env state (the unpacked tensors; for a packed batch views of the state behind the properties below)
+        self._buffers = torch.zeros((E, s.N, s.DW), dtype=torch.int32, device=dev)
         if s.kind == COMB:
-            self.channels = torch.zeros((E, s.N), dtype=_MASK_DTYPE[s.mask_bytes], device=dev)
+            self._channels = torch.zeros((E, s.N), dtype=_MASK_DTYPE[s.mask_bytes], device=dev)
             self.sel_quality = self.sel_count = None
         elif s.kind == SINGLE:
             # per-agent channel bit; sel_quality / sel_count hold channel_errors / n_collisions
-            self.channels = torch.zeros((E, s.N), dtype=torch.uint8, device=dev)
+            self._channels = torch.zeros((E, s.N), dtype=torch.uint8, device=dev)
             self.sel_quality = torch.zeros((E,), dtype=torch.int32, device=dev)
             self.sel_count = torch.zeros((E,), dtype=torch.int32, device=dev)
         else:
-            self.channels = torch.zeros((E,), dtype=torch.int32, device=dev)
+            self._channels = torch.zeros((E,), dtype=torch.int32, device=dev)
             self.sel_quality = torch.zeros((E,), dtype=torch.int32, device=dev)
             self.sel_count = torch.zeros((E,), dtype=torch.int32, device=dev)
-        self.received = torch.zeros((E, s.N), dtype=torch.int32, device=dev)
-        self.discarded = torch.zeros((E, s.N), dtype=torch.int32, device=dev)
+        self._received = torch.zeros((E, s.N), dtype=torch.int32, device=dev)
+        self._discarded = torch.zeros((E, s.N), dtype=torch.int32, device=dev)
+        # packed state: the truth from construction on for an eligible spec (all-zero state is the same in
+        # both layouts).  _in_packed: the truth is in the packed tensors (until a step could take a counter
+        # past 16 bits; a reset returns to it).  _ver counts the state-changing calls on the host, _unpacked_ver
+        # is the _ver the unpacked tensors were last refreshed at: several reads between two steps, one unpack
+        self.packed = packed is None and packed_eligible(s)
+        self._in_packed = self.packed
+        self._ver = self._unpacked_ver = 0
+        self._max_x = 1
+        self._rows = self._counters = self.pst = None
+        if self.packed:
+            self._rows = torch.zeros((E, s.N, s.DW), dtype=torch.int32, device=dev)
+            self._counters = torch.zeros((E, s.N), dtype=torch.int32, device=dev)
+            self.pst = _lib.EnvPackedState(self._rows.data_ptr(), self._counters.data_ptr())
         # persistent outputs (overwritten by every call unless `out_*` is given)
         self.obs = torch.zeros((E, s.N, s.F), dtype=torch.float32, device=dev)
         self.reward = torch.zeros((E,), dtype=torch.int32, device=dev)
@@ -72,12 +104,63 @@ class EnvBatch:
             self._kinds_host.ctypes.data, self._period_host.ctypes.data, self._offset_host.ctypes.data,
             None if self.gather is None else self.gather.data_ptr(), self.rng_off.data_ptr(),
             self.poisson_cdf.data_ptr())
-        self.st = _lib.EnvState(self.buffers.data_ptr(), self.channels.data_ptr(), self.received.data_ptr(),
-                                self.discarded.data_ptr(),
+        self.st = _lib.EnvState(self._buffers.data_ptr(), self._channels.data_ptr(), self._received.data_ptr(),
+                                self._discarded.data_ptr(),
                                 None if self.sel_quality is None else self.sel_quality.data_ptr(),
                                 None if self.sel_count is None else self.sel_count.data_ptr())
         self.rng_step = 0
         self.timestep = 0
+
+    # -------------------------------------------------------------- state
+    def sync_unpacked(self, stream=None):
+        """Bring the unpacked tensors (self.st) up to date with a packed state: one d2d_env_state_unpack launch
+        on the current stream when they are stale -- no allocation, no synchronisation, graph-capturable."""
+        if self._in_packed and self._unpacked_ver != self._ver:
+            rc = self.lib.d2d_env_state_unpack(self.desc, self.pst, self.st, _lib.stream_ptr(stream))
+            _lib.check(rc, "d2d_env_state_unpack")
+            self._unpacked_ver = self._ver
+
+    def commit_unpacked(self, stream=None):
+        """After a native call that stepped self.st directly (preceded by sync_unpacked): pack the result back
+        into the state (d2d_env_state_pack)."""
+        self._ver += 1
+        if self._in_packed:
+            rc = self.lib.d2d_env_state_pack(self.desc, self.st, self.pst, _lib.stream_ptr(stream))
+            _lib.check(rc, "d2d_env_state_pack")
+            self._unpacked_ver = self._ver
+
+    @property
+    def packed_now(self):
+        """True while the packed tensors are the state (False for an unpacked batch, and between the step that
+        could take a counter past 16 bits and the next reset)."""
+        return self._in_packed
+
+    @property
+    def buffers(self):
+        """uint32 rows [E][N][DW] (read-only view of the state for a packed batch)."""
+        self.sync_unpacked()
+        return self._buffers
+
+    @property
+    def channels(self):
+        self.sync_unpacked()
+        return self._channels
+
+    @property
+    def received(self):
+        self.sync_unpacked()
+        return self._received
+
+    @property
+    def discarded(self):
+        self.sync_unpacked()
+        return self._discarded
+
+    def _arrival_max(self, replay_arrivals):
+        # the largest arrival one call can add to `received`: buffer cells are bytes and the Poisson draw
+        # returns <= 255; a Bernoulli draw adds 0 or 1
+        poisson = bool(np.any(self._kinds_host == _lib.D2D_ARRIVAL_POISSON))
+        return 255 if (poisson or replay_arrivals is not None) else 1
 
     # ------------------------------------------------------------ buffers
     @property
@@ -189,8 +272,16 @@ class EnvBatch:
               stream=None, out_state_bf16=None):
         o, res = self._out(want_obs, want_state, False, False, out_obs, out_state, None, out_state_bf16=out_state_bf16)
         rp, _keep = self._replay(None if replay_arrivals is None else (None, replay_arrivals))
-        rc = self.lib.d2d_env_reset(self.desc, self.st, rp, o, self.rng_step, _lib.stream_ptr(stream))
-        _lib.check(rc, "d2d_env_reset")
+        if self.packed:
+            # a reset overwrites the whole state: back on the packed path without a pack
+            rc = self.lib.d2d_env_reset_packed(self.desc, self.pst, rp, o, self.rng_step, _lib.stream_ptr(stream))
+            _lib.check(rc, "d2d_env_reset_packed")
+            self._in_packed = True
+            self._max_x = self._arrival_max(replay_arrivals)
+        else:
+            rc = self.lib.d2d_env_reset(self.desc, self.st, rp, o, self.rng_step, _lib.stream_ptr(stream))
+            _lib.check(rc, "d2d_env_reset")
+        self._ver += 1
         self.rng_step += 1
         self.timestep = 0
         res.pop("reward")
@@ -205,10 +296,23 @@ class EnvBatch:
         o, res = self._out(want_obs, want_state, want_ack, want_success, out_obs, out_state, out_reward,
                            out_state_bf16=out_state_bf16)
         rp, _keep = self._replay(replay)
+        if self._in_packed:
+            # discarded <= received <= (steps since reset + 1) * max arrival per call: before the step that could
+            # take that past 16 bits, unpack once and run unpacked until the next reset
+            self._max_x = max(self._max_x, self._arrival_max(None if replay is None else replay[1]))
+            if (self.timestep + 2) * self._max_x > _COUNTER_MAX:
+                self.sync_unpacked(stream)
+                self._in_packed = False
         self.timestep += 1
-        rc = self.lib.d2d_env_step(self.desc, self.st, actions.data_ptr(), rp, o, self.timestep, self.rng_step,
-                                   _lib.stream_ptr(stream))
-        _lib.check(rc, "d2d_env_step")
+        if self._in_packed:
+            rc = self.lib.d2d_env_step_packed(self.desc, self.pst, actions.data_ptr(), rp, o, self.timestep,
+                                              self.rng_step, _lib.stream_ptr(stream))
+            _lib.check(rc, "d2d_env_step_packed")
+        else:
+            rc = self.lib.d2d_env_step(self.desc, self.st, actions.data_ptr(), rp, o, self.timestep, self.rng_step,
+                                       _lib.stream_ptr(stream))
+            _lib.check(rc, "d2d_env_step")
+        self._ver += 1
         self.rng_step += 1
         res["done"] = self.timestep >= s.episode_length
         return res
@@ -218,18 +322,26 @@ class EnvBatch:
         """step() into the compact record out_record, fused with the MLP policy of the next slot on that record
         (d2d_comb_policy_fused_step, one launch): actions_out [E][N] and logp_out [N][E] of slot t + 1, drawn at
         the rng_step the two-call sequence (step, then the policy) gives it -- bit-identical results.  mlp_desc:
-        an actor-only d2d_mlp_desc on this batch's record (obs_format D2D_OBS_U8)."""
+        an actor-only d2d_mlp_desc on this batch's record (obs_format D2D_OBS_U8).  The fused kernel steps the
+        unpacked state: a packed batch unpacks, calls it and packs again (off the product path)."""
         s = self.spec
         dt = _MASK_DTYPE[s.mask_bytes] if s.kind == COMB else torch.uint8
         self._check_out(actions, (self.E, s.N), dt, "actions")
         self._check_out(actions_out, (self.E, s.N), dt, "actions_out")
         self._check_out(logp_out, (s.N, self.E), torch.float32, "logp_out")
         o, res = self._out(False, False, False, False, out_record, None, out_reward)
+        if self._in_packed:
+            self._max_x = max(self._max_x, self._arrival_max(None))
+            if (self.timestep + 2) * self._max_x > _COUNTER_MAX:
+                self.sync_unpacked(stream)
+                self._in_packed = False
+        self.sync_unpacked(stream)
         self.timestep += 1
         rc = self.lib.d2d_comb_policy_fused_step(self.desc, self.st, actions.data_ptr(), o, self.timestep,
                                                  self.rng_step, mlp_desc, self.rng_step + 1, 1 if deterministic else 0,
                                                  actions_out.data_ptr(), logp_out.data_ptr(), _lib.stream_ptr(stream))
         _lib.check(rc, "d2d_comb_policy_fused_step")
+        self.commit_unpacked(stream)
         self.rng_step += 1
         res["done"] = self.timestep >= s.episode_length
         return res

@@ -52,7 +52,9 @@ extern "C" {
                               13: d2d_comb_policy_fused_step, D2D_OPT_FUSED_SLICE, d2d_env_out.state_bf16;
                               14: d2d_policy_gru_carry, d2d_gru_carry_floats, d2d_central_critic_dw1, single obs_record;
                               15: actions = NULL in forced mode (d2d_policy_mlp_step, d2d_policy_gru);
-                              still 15, additive: d2d_rdqn_q, d2d_rdqn_grad, d2d_rdqn_grad_workspace (iRDQN) */
+                              still 15, additive: d2d_rdqn_q, d2d_rdqn_grad, d2d_rdqn_grad_workspace (iRDQN);
+                              still 15, additive: d2d_env_packed_state, d2d_env_reset_packed, d2d_env_step_packed,
+                              d2d_env_state_pack, d2d_env_state_unpack (no layout change) */
 
 enum { D2D_ENV_COMBINATORIAL = 0, D2D_ENV_CHANNEL_SELECTION = 1, D2D_ENV_SINGLE = 2 };
 enum { D2D_ARRIVAL_POISSON = 0, D2D_ARRIVAL_SCHEDULED_BERNOULLI = 1, D2D_ARRIVAL_NONE = 2 };
@@ -163,6 +165,41 @@ int d2d_env_reset(const d2d_env_desc* desc, const d2d_env_state* st, const d2d_e
 int d2d_env_step(const d2d_env_desc* desc, const d2d_env_state* st, const void* actions,
                  const d2d_env_replay* replay, const d2d_env_out* out, int32_t timestep, uint32_t rng_step,
                  void* stream);
+
+/* ---- Packed per-agent state of the combinatorial env (added on top of ABI v15 without a layout change:
+ * new entry points and one new struct only, d2d_abi_version() stays 15) ----
+ * The step is bound by the bytes it moves; the packed state moves 10 fewer per agent-step:
+ *   rows      uint32 [E][N][DW]  the buffer row as in d2d_env_state.buffers, with the agent's channel mask
+ *                                (d2d_env_state.channels) in the top d2d_mask_bytes(C) bytes of word DW-1
+ *   counters  uint32 [E][N]      received in bits 0-15, discarded in bits 16-31
+ * All-zero state is the same in both layouts.
+ * Eligibility, checked before any HIP call (else D2D_EUNSUPPORTED, the caller stays on d2d_env_state):
+ *   the combinatorial env with max_deadline + d2d_mask_bytes(C) <= 4 * d2d_buffer_words(max_deadline)
+ *   (D = 14 or 7 with C = 8 qualify, D = 8 or 16 do not) and C <= 8 (the uint16 / uint32-mask kernels were not
+ *   instantiated packed).
+ * Counter bound: the caller keeps both counters below 65,536.  discarded <= received <= (steps since reset + 1)
+ * * max arrival per call (255: buffer cells are bytes; 1 without Poisson agents and replayed arrivals); before
+ * a step that could pass it the caller unpacks and continues on d2d_env_step until the next reset. */
+typedef struct d2d_env_packed_state {
+    uint32_t* rows;
+    uint32_t* counters;
+} d2d_env_packed_state;
+
+/* d2d_env_reset / d2d_env_step on the packed state: same arguments, outputs (record, obs, state, bf16 state, ack,
+ * success, reward) and Philox stream; only the state load and store differ. */
+int d2d_env_reset_packed(const d2d_env_desc* desc, const d2d_env_packed_state* st, const d2d_env_replay* replay,
+                         const d2d_env_out* out, uint32_t rng_step, void* stream);
+int d2d_env_step_packed(const d2d_env_desc* desc, const d2d_env_packed_state* st, const void* actions,
+                        const d2d_env_replay* replay, const d2d_env_out* out, int32_t timestep, uint32_t rng_step,
+                        void* stream);
+
+/* Elementwise conversions, one lane per agent row (sel_quality / sel_count are not used): unpacked -> packed
+ * (counters truncated to 16 bits: see the bound) and packed -> unpacked.  For reading the state as the public
+ * tensors and for the native paths that stay unpacked (d2d_comb_policy_fused_step). */
+int d2d_env_state_pack(const d2d_env_desc* desc, const d2d_env_state* src, const d2d_env_packed_state* dst,
+                       void* stream);
+int d2d_env_state_unpack(const d2d_env_desc* desc, const d2d_env_packed_state* src, const d2d_env_state* dst,
+                         void* stream);
 
 /* Synthetic actions (env-only benchmark; replaces the per-agent
  * np.random.binomial of baselines.CombinatorialRandomAccess.act,
