@@ -8,6 +8,11 @@ agent-batched on the MI355X (csrc/rdqn_kernels.hip through d2dhip/rdqn.py):
     (the reference: N batch-1 GRU forwards per slot, irdqn.py:244-253), then the env-step kernel;
   * replay: a device ring per env timeline, episode_length + 1 obs rows per episode (the reset obs and every next
     obs), so transition t's state is row t of its episode and its successor state row t + 1 -- s' is not stored twice;
+    fp32 rows by default, or (replay_record=True / D2D_RDQN_RECORD=1) the env kernel's compact obs record, 32 bytes
+    per agent row instead of 4 * obs_dim, with bit-identical results;
+  * acting state: while a slot's window is still an episode prefix (t + 1 <= history_len) its hidden state is the
+    previous slot's plus one GRU step, so the launch carries it (d2dhip.rdqn.CarryState) instead of recomputing the
+    window, bit for bit the same actions (carry_state / D2D_RDQN_CARRY=0 turns it off);
   * update: one d2d_rdqn_q launch on the target parameters (max_a Q'(s')), one d2d_rdqn_grad launch (TD loss and
     BPTT gradients of all N agents, written into .grad) and one Adam step over the agent-stacked parameters (the
     reference: N x (two GRU forwards, one backward, one Adam step), irdqn.py:290-300).
@@ -17,6 +22,7 @@ DESIGN.md §4.9.  Not implemented: a callable `loss` (NotImplementedError); shap
 (hidden <= 128, obs + 1 <= 64, n_channels <= 16, history_len <= 256) raise NotImplementedError.
 """
 import math
+import os
 import random
 from collections import deque, namedtuple
 
@@ -238,10 +244,15 @@ class DQN:
 
 
 class iRDQN(BatchedLearnerBase):
+    # the replay / test rings as the compact obs record instead of fp32 rows (the same results, a quarter of the bytes)
+    replay_record = os.environ.get("D2D_RDQN_RECORD", "0") == "1"
+    # acting slots carry their hidden state while the window is an episode prefix (the same results, fewer GRU steps)
+    carry_state = os.environ.get("D2D_RDQN_CARRY", "1") != "0"
+
     def __init__(self, env, history_len=5, replay_start_size=50000, replay_buffer_size=1000000, gamma=0.99,
                  update_target_frequency=10000, minibatch_size=32, learning_rate=1e-3, update_frequency=1,
                  initial_exploration_rate=1, final_exploration_rate=0.1, adam_epsilon=1e-8, loss='huber',
-                 early_stopping=True):
+                 early_stopping=True, *, replay_record=None):
         self.device = self._resolve_device(None)
         if self.device.type != "cuda":
             import d2dhip
@@ -249,6 +260,9 @@ class iRDQN(BatchedLearnerBase):
         if callable(loss):
             raise NotImplementedError("iRDQN on the HIP kernels implements loss 'huber' and 'mse', not a callable")
         self.history_len = history_len
+        if replay_record is not None:
+            self.replay_record = bool(replay_record)
+        self._carries = {}        # (id(batch), role) -> rdqn.CarryState
         self.replay_start_size = replay_start_size
         self.replay_buffer_size = replay_buffer_size
         self.replay_buffer = ReplayBuffer(self.replay_buffer_size, self.device)  # reference attribute; unused here
@@ -302,10 +316,28 @@ class iRDQN(BatchedLearnerBase):
         n_ep = min(n_waves, -(-cap // T) + 1)
         self._cap = min(cap, n_waves * T)
         self._ring_ep = n_ep
-        self._ring = torch.zeros((n_ep * (T + 1), E, s.N, s.F), dtype=torch.float32, device=dev)
+        self._ring = self._obs_ring(b, n_ep * (T + 1))
         self._act_ring = torch.zeros((n_ep * T, E, s.N), dtype=b.action_buffer().dtype, device=dev)
         self._rew_ring = torch.zeros((n_ep * T, E), dtype=torch.int32, device=dev)
         self._added = 0           # transitions written per env so far
+
+    def _obs_ring(self, b, rows):
+        """A zeroed obs ring [rows][E][N][F]: fp32 rows, or the env batch's compact record (replay_record)."""
+        if self.replay_record:
+            return b.record_buffer((rows,))
+        s = b.spec
+        return torch.zeros((rows, b.E, s.N, s.F), dtype=torch.float32, device=self.device)
+
+    def _carry(self, b, role):
+        """The CarryState of (batch, role), or None with carry_state off."""
+        if not self.carry_state:
+            return None
+        from d2dhip import rdqn
+        key = (id(b), role)
+        carries = self.__dict__.setdefault("_carries", {})
+        if key not in carries:
+            carries[key] = rdqn.CarryState()
+        return carries[key]
 
     def _sample_chunks(self, n_envs, length, batch_size, chunk_size):
         """Host draw of one minibatch's chunks: (env [B], start [B]), start uniform in [0, length - chunk_size) of
@@ -351,8 +383,9 @@ class iRDQN(BatchedLearnerBase):
         self.n_syncs += 1
 
     # -------------------------------------------------------------- rollout
-    def _act_slot(self, b, ring, row, S, act_out, mode, eps_rows=None):
-        """One d2d_rdqn_q launch: every agent's action in every env on the window of the last S rows ending at `row`."""
+    def _act_slot(self, b, ring, row, S, act_out, mode, eps_rows=None, carry=None):
+        """One d2d_rdqn_q_ex launch: every agent's action in every env on the window of the last S rows ending at
+        `row`; with `carry`, on the previous slot's hidden state where this window extends that slot's by one row."""
         from d2dhip import rdqn
         E = b.E
         key = (id(b), E)
@@ -362,9 +395,11 @@ class iRDQN(BatchedLearnerBase):
             self._slot_samples[:, 0] = torch.arange(E, dtype=torch.int32, device=self.device)
         self._slot_samples[:, 1] = row
         self._slot_samples[:, 2] = S
-        rdqn.q_values(self.network.data(), ring, self._slot_samples, mode=mode, eps_rows=eps_rows,
+        # the Parameters themselves, not .data(): their _version counters are part of the carry's tag
+        rdqn.q_values(self.network.params, ring, self._slot_samples, mode=mode, eps_rows=eps_rows,
                       rng_step=b.rng_step, seed=self._policy_seed(), env_base=b.desc.env_base,
-                      rng_offset=b.rng_off.data_ptr(), want_q=False, want_qmax=False, out={"action": act_out})
+                      rng_offset=b.rng_off.data_ptr(), want_q=False, want_qmax=False, out={"action": act_out},
+                      carry=carry, row=row, window=S)
         return act_out
 
     def _train_wave(self, b, ep0):
@@ -378,11 +413,14 @@ class iRDQN(BatchedLearnerBase):
                                 device=self.device)
         slot = (self._added // T) % self._ring_ep
         r0, m0 = slot * (T + 1), slot * T
+        carry = self._carry(b, "train")
         with torch.no_grad():
             b.reset(want_obs=True, out_obs=self._ring[r0])
+            if carry is not None:
+                carry.reset()     # a new episode: slot 0 recomputes whatever was written to the parameters since
             for t in range(T):
                 act = self._act_slot(b, self._ring, r0 + t, min(t + 1, L), self._act_ring[m0 + t], "eps",
-                                     eps_first if t == 0 else eps_rest)
+                                     eps_first if t == 0 else eps_rest, carry=carry)
                 b.step(act, want_obs=True, out_obs=self._ring[r0 + t + 1], out_reward=self._rew_ring[m0 + t])
             env.timestep = b.timestep
             recv, disc = b.received.sum(1).double(), b.discarded.sum(1).double()
@@ -443,7 +481,8 @@ class iRDQN(BatchedLearnerBase):
         s = b.spec
         waves = max(1, math.ceil(n_episodes / E))
         tf = self._teacher_tensors(teacher, b, waves) if teacher is not None else None
-        ring = torch.zeros((T + 1, E, s.N, s.F), dtype=torch.float32, device=self.device)
+        ring = self._obs_ring(b, T + 1)
+        carry = self._carry(b, "test")
         acts = torch.zeros((waves * T, E, s.N), dtype=b.action_buffer().dtype, device=self.device)
         rew = torch.zeros((waves * T, E), dtype=torch.int32, device=self.device)
         recv = torch.zeros((waves, E), dtype=torch.float64, device=self.device)
@@ -452,9 +491,11 @@ class iRDQN(BatchedLearnerBase):
             for w in range(waves):
                 b.reset(want_obs=True, out_obs=ring[0],
                         replay_arrivals=None if tf is None else tf["reset_arrivals"][w])
+                if carry is not None:
+                    carry.reset()
                 for t in range(T):
                     i = w * T + t
-                    act = self._act_slot(b, ring, t, min(t + 1, L), acts[i], "greedy")
+                    act = self._act_slot(b, ring, t, min(t + 1, L), acts[i], "greedy", carry=carry)
                     b.step(act, want_obs=True, out_obs=ring[t + 1], out_reward=rew[i],
                            replay=None if tf is None else tf["replay"][i])
                 env.timestep = b.timestep

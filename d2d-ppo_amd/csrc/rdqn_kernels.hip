@@ -27,7 +27,12 @@
 // and BPTT, which overwrites each step's gates with its pre-activation gradients.  (2) rdqn_wgrad_kernel, one wave
 // per 16 x 16 tile of a gradient tensor: dW = sum over (step, sample) of dpre (x) input as MFMA products over the
 // workspace images, in a fixed order with no atomics -- bitwise reproducible.
+//
+// Observations enter through load_x alone: fp32 ring rows, or (d2d_rdqn_q_ex / d2d_rdqn_grad_ex, D2D_OBS_U8) the env
+// kernel's compact record decoded to the same floats.  d2d_rdqn_q_ex can also keep every sample's final h in a
+// scratch (hcarry) and start the next acting slot from it -- one GRU step instead of the window, the same arithmetic.
 #include <algorithm>
+#include <string>
 
 #include "common.h"
 #include "gru_common.h"
@@ -42,7 +47,7 @@ struct RdqnArgs {
   int N, E, F, H, A, HT, IT;
   int vecF, vecH;              // 16-byte fragment loads of F-wide / H-wide rows
   const float *w_ih, *w_hh, *b_ih, *b_hh, *w1, *b1, *w2, *b2, *w3, *b3;
-  const float* obs;            // ring [rows][E][N][F]
+  const float* obs;            // ring [rows][E][N][F] (fp32 rows; else rec below)
   int rows, ep_len, shift;     // ep_len > 0: window indices are transitions, row = m + m / ep_len + shift
   int ntrans;                  // ep_len > 0: transitions the ring holds per env
   const int32_t* samples;      // [B][3] env, last, window length
@@ -65,6 +70,12 @@ struct RdqnArgs {
   const uint8_t* done;
   float *g_w_ih, *g_w_hh, *g_b_ih, *g_b_hh, *g_w1, *g_b1, *g_w2, *g_b2, *g_w3, *g_b3, *loss;
   float *ws_x, *ws_h, *ws_g, *ws_y1, *ws_y2, *ws_d1, *ws_d2, *ws_dq, *ws_loss;
+  // the kernels' REC / CARRY instances only (after the fields every instance reads, which keep their offsets)
+  const uint8_t* rec;          // the compact record [rows][E][N][RB] (D2D_OBS_U8) in place of obs, with
+  const uint32_t* sgn;         // its int8-column masks [N][RB / 32]
+  int RB;
+  int carry_in;                // h0 = hcarry and one step on row `last` instead of the whole window
+  float* hcarry;               // [N][tiles][HT][64] f32x4: the final h image of every (agent, tile)
 };
 
 // W[row][col .. col + 3] of a [rows][cols] matrix, zeros outside (col % 4 == 0)
@@ -136,9 +147,47 @@ __device__ __forceinline__ int ring_row(const RdqnArgs& a, int m) {
   return m < 0 ? m + a.rows : m;
 }
 
-// x image of one window step: lane (g, i) <- x[sample i][16q + 4g + r]; zero: the window has not started
-__device__ __forceinline__ void load_x(const RdqnArgs& a, f32x4* xs, int k, int env, int m, bool zero, int lane) {
+// agent k's int8-column masks of the record (workgroup-uniform: scalar registers, as XSigns of gru_common.h);
+// RB <= 64, so two words.  REC: the kernel instance that reads the record -- the fp32 instances carry none of this.
+template <bool REC>
+struct RecSigns {
+  uint32_t w[2];
+  __device__ __forceinline__ RecSigns(const RdqnArgs& a, int k) {
+    w[0] = w[1] = 0u;
+    if constexpr (REC) {
+      const int nw = a.RB >> 5;
+      w[0] = __builtin_amdgcn_readfirstlane(a.sgn[(size_t)k * nw]);
+      if (nw > 1) w[1] = __builtin_amdgcn_readfirstlane(a.sgn[(size_t)k * nw + 1]);
+    }
+  }
+  // flags of columns col .. col + 3 (col % 4 == 0, col < 64)
+  __device__ __forceinline__ uint32_t bits4(int col) const { return ((col < 32 ? w[0] : w[1]) >> (col & 31)) & 0xFu; }
+};
+
+// x image of one window step: lane (g, i) <- x[sample i][16q + 4g + r]; zero: the window has not started.
+// Record rows: one aligned dword per (q, lane) at byte 16q + 4g (inside the row: 16 IT <= RB), decoded as the MLP
+// kernels do; columns >= F are forced to 0 -- byte F is those kernels' bias input 1, and the GRU here has its own
+// biases -- so the image, and ws_x after it, equal the fp32 path's on the decoded row.
+template <bool REC>
+__device__ __forceinline__ void load_x(const RdqnArgs& a, f32x4* xs, int k, int env, int m, bool zero,
+                                       const RecSigns<REC>& sg, int lane) {
   const int g = lane >> 4;
+  if constexpr (REC) {
+    const size_t r = ((size_t)ring_row(a, m) * a.E + env) * a.N + k;
+    const uint8_t* row = a.rec + r * a.RB;
+    for (int q = 0; q < a.IT; ++q) {
+      const int col = 16 * q + 4 * g;
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (!zero) {
+        const uint32_t w = *reinterpret_cast<const uint32_t*>(row + col);
+        const uint32_t sm = sign_bytes(sg.bits4(col));
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = col + e < a.F ? rec_byte(w, e, sm) : 0.f;
+      }
+      xs[q * 64 + lane] = v;
+    }
+    return;
+  }
   const float* row = a.obs + (((size_t)ring_row(a, m) * a.E + env) * a.N + k) * a.F;
   for (int q = 0; q < a.IT; ++q) {
     f32x4 v = {0.f, 0.f, 0.f, 0.f};
@@ -240,6 +289,9 @@ __device__ __forceinline__ Best q_best(f32x4 q, int A, int lane) {
 }
 
 // ------------------------------------------------------------------------------------------ Q / acting
+// REC: observations from the compact record.  CARRY: hcarry is given -- the final h is stored there, and with
+// carry_in the window is the carried h plus one step.  <false, false> is the kernel of d2d_rdqn_q as it always was.
+template <bool REC, bool CARRY>
 __global__ __launch_bounds__(64) void rdqn_q_kernel(const RdqnArgs a) {
   __shared__ f32x4 xs[kMaxIT * 64], hb[3][kMaxHT * 64], qs[64];
   const int lane = threadIdx.x, g = lane >> 4, i = lane & 15;
@@ -253,17 +305,25 @@ __global__ __launch_bounds__(64) void rdqn_q_kernel(const RdqnArgs a) {
 #pragma unroll
   for (int m = 1; m <= 8; m <<= 1) Smax = max(Smax, __shfl_xor(Smax, m));
   Smax = __builtin_amdgcn_readfirstlane(Smax);
-  for (int t = 0; t < a.HT; ++t) hb[0][t * 64 + lane] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const RecSigns<REC> sg(a, k);
+  // carried state: this (agent, tile)'s h image as the previous launch left it (the contract of d2d_rdqn_q_ex)
+  const bool cin = CARRY && a.carry_in != 0;
+  f32x4* hc = nullptr;
+  if constexpr (CARRY) hc = reinterpret_cast<f32x4*>(a.hcarry) + ((size_t)k * gridDim.x + blockIdx.x) * a.HT * 64;
+  for (int t = 0; t < a.HT; ++t) hb[0][t * 64 + lane] = cin ? hc[t * 64 + lane] : f32x4{0.f, 0.f, 0.f, 0.f};
   int cur = 0;
-  for (int j = 0; j < Smax; ++j) {
-    const int rel = j - (Smax - S);  // step of this sample's own window (right-aligned)
+  const int steps = cin ? 1 : Smax;  // carry-in: the one new row of every sample, on the carried h
+  for (int j = 0; j < steps; ++j) {
+    const int rel = cin ? S - 1 : j - (Smax - S);  // step of this sample's own window (right-aligned)
     const bool active = rel >= 0;
-    load_x(a, xs, k, env, last - S + 1 + max(rel, 0), !active, lane);
+    load_x<REC>(a, xs, k, env, last - S + 1 + max(rel, 0), !active, sg, lane);
     wave_sync();
-    gru_step(a, k, xs, hb[cur], hb[cur ^ 1], j == 0, active, nullptr, lane);
+    gru_step(a, k, xs, hb[cur], hb[cur ^ 1], !cin && j == 0, active, nullptr, lane);
     wave_sync();
     cur ^= 1;
   }
+  if constexpr (CARRY)
+    for (int t = 0; t < a.HT; ++t) hc[t * 64 + lane] = hb[cur][t * 64 + lane];
   const f32x4 q = head_fwd(a, k, hb[cur], hb[cur ^ 1], hb[2], qs, lane);
   if (ok && a.q) {
 #pragma unroll
@@ -292,6 +352,7 @@ __global__ __launch_bounds__(64) void rdqn_q_kernel(const RdqnArgs a) {
 
 // ------------------------------------------------------------------------------------------ TD gradients
 // forward + loss + backward of one 16-sample tile of agent k (see the file comment)
+template <bool REC>
 __global__ __launch_bounds__(64) void rdqn_bptt_kernel(const RdqnArgs a) {
   __shared__ f32x4 xs[kMaxIT * 64], hb[3][kMaxHT * 64], dgs[3][kMaxHT * 64], qs[64];
   const int lane = threadIdx.x, g = lane >> 4, i = lane & 15;
@@ -311,8 +372,9 @@ __global__ __launch_bounds__(64) void rdqn_bptt_kernel(const RdqnArgs a) {
     *reinterpret_cast<f32x4*>(wh + (size_t)b * HW + 16 * t + 4 * g) = f32x4{0.f, 0.f, 0.f, 0.f};
   }
   int cur = 0;
+  const RecSigns<REC> sg(a, k);
   for (int j = 0; j < L; ++j) {
-    load_x(a, xs, k, env, last - L + 1 + j, false, lane);
+    load_x<REC>(a, xs, k, env, last - L + 1 + j, false, sg, lane);
     for (int q = 0; q < a.IT; ++q)
       *reinterpret_cast<f32x4*>(wx + ((size_t)j * Bp + b) * IW + 16 * q + 4 * g) = xs[q * 64 + lane];
     wave_sync();
@@ -591,7 +653,8 @@ int check_desc(const d2d_rdqn_desc* d, const char* fn) {
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-RdqnArgs make_args(const d2d_rdqn_desc* d, const float* obs, const int32_t* samples, int B, int shift) {
+RdqnArgs make_args(const d2d_rdqn_desc* d, const float* obs, const uint8_t* rec, const uint32_t* sgn,
+                   const int32_t* samples, int B, int shift) {
   RdqnArgs a = {};
   a.N = d->n_agents; a.E = d->n_envs; a.F = d->obs_dim; a.H = d->hidden; a.A = d->n_out;
   a.HT = (a.H + 15) / 16; a.IT = (a.F + 15) / 16;
@@ -599,11 +662,23 @@ RdqnArgs make_args(const d2d_rdqn_desc* d, const float* obs, const int32_t* samp
   a.vecH = a.H % 4 == 0 && aligned16(d->w_hh) && aligned16(d->w1) && aligned16(d->w2) && aligned16(d->w3);
   a.w_ih = d->w_ih; a.w_hh = d->w_hh; a.b_ih = d->b_ih; a.b_hh = d->b_hh;
   a.w1 = d->w1; a.b1 = d->b1; a.w2 = d->w2; a.b2 = d->b2; a.w3 = d->w3; a.b3 = d->b3;
-  a.obs = obs; a.rows = d->ring_rows; a.ep_len = d->ring_episode; a.shift = shift;
+  a.obs = obs; a.rec = rec; a.sgn = sgn; a.RB = D2D_RECORD_BYTES(a.F);
+  a.rows = d->ring_rows; a.ep_len = d->ring_episode; a.shift = shift;
   a.ntrans = a.ep_len > 0 ? a.rows / (a.ep_len + 1) * a.ep_len : 0;
   a.samples = samples; a.B = B; a.mask_bytes = a.A <= 8 ? 1 : 2;
   a.seed = d->seed; a.env_base = d->env_base; a.rng_off = d->rng_offset;
   return a;
+}
+
+// obs_format_args with the entry point's name in front of its error text
+int obs_args(const char* fn, int32_t format, const uint32_t* sgn_in, int32_t obs_dim, const void* obs, const float*& f32,
+             const uint8_t*& rec, const uint32_t*& sgn) {
+  const int rc = obs_format_args(format, sgn_in, obs_dim, obs, f32, rec, sgn);
+  if (rc) {
+    const std::string why = d2d_last_error();
+    d2d_set_error("%s: %s", fn, why.c_str());
+  }
+  return rc;
 }
 
 }  // namespace
@@ -611,30 +686,58 @@ RdqnArgs make_args(const d2d_rdqn_desc* d, const float* obs, const int32_t* samp
 
 using namespace d2d;
 
-extern "C" int d2d_rdqn_q(const d2d_rdqn_desc* d, const float* obs, const int32_t* samples, int32_t B,
-                          int32_t row_shift, int32_t mode, float eps, const float* eps_rows, int32_t ready,
-                          const uint8_t* explore_mask, const uint8_t* explore_action, uint32_t rng_step, float* q, float* qmax, void* action,
-                          void* stream) {
-  int rc = check_desc(d, "d2d_rdqn_q");
+extern "C" int64_t d2d_rdqn_carry_floats(const d2d_rdqn_desc* d, int32_t B) {
+  if (!d || B < 0 || d->n_agents < 0 || d->hidden < 1 || d->hidden > 16 * kMaxHT) return -1;
+  return (int64_t)d->n_agents * (16 * (((int64_t)B + 15) / 16)) * (16 * ((d->hidden + 15) / 16));
+}
+
+extern "C" int d2d_rdqn_q_ex(const d2d_rdqn_desc* d, const void* obs, int32_t obs_format, const uint32_t* obs_signed,
+                             const int32_t* samples, int32_t B, int32_t row_shift, int32_t mode, float eps,
+                             const float* eps_rows, int32_t ready, const uint8_t* explore_mask,
+                             const uint8_t* explore_action, uint32_t rng_step, float* hcarry, int32_t carry_in,
+                             float* q, float* qmax, void* action, void* stream) {
+  const char* fn = "d2d_rdqn_q";
+  int rc = check_desc(d, fn);
   if (rc) return rc;
   if (!obs || !samples || B < 0 || row_shift < 0 || row_shift > 1) {
     d2d_set_error("d2d_rdqn_q: NULL obs / samples, negative B or row_shift outside {0, 1}");
     return D2D_EINVAL;
   }
+  const float* f32;
+  const uint8_t* rec;
+  const uint32_t* sgn;
+  rc = obs_args(fn, obs_format, obs_signed, d->obs_dim, obs, f32, rec, sgn);
+  if (rc) return rc;
   if (mode < D2D_RDQN_GREEDY || mode > D2D_RDQN_FORCED) { d2d_set_error("d2d_rdqn_q: unknown mode %d", mode); return D2D_EINVAL; }
   if (mode == D2D_RDQN_FORCED && action && (!explore_mask || !explore_action)) {
     d2d_set_error("d2d_rdqn_q: forced mode needs explore_mask and explore_action");
     return D2D_EINVAL;
   }
   if (mode == D2D_RDQN_EPS && !(eps >= 0.f && eps <= 1.f)) { d2d_set_error("d2d_rdqn_q: eps outside [0, 1]"); return D2D_EINVAL; }
+  if (carry_in && !hcarry) { d2d_set_error("d2d_rdqn_q: carry_in needs hcarry"); return D2D_EINVAL; }
+  if (carry_in && row_shift != 0) { d2d_set_error("d2d_rdqn_q: carry_in needs row_shift 0"); return D2D_EINVAL; }
+  if (hcarry && !aligned16(hcarry)) { d2d_set_error("d2d_rdqn_q: hcarry must be 16-byte aligned"); return D2D_EINVAL; }
   if (B == 0 || d->n_agents == 0) return D2D_OK;
-  RdqnArgs a = make_args(d, obs, samples, B, row_shift);
+  RdqnArgs a = make_args(d, f32, rec, sgn, samples, B, row_shift);
   a.mode = mode; a.ready = ready ? 1 : 0; a.eps = eps; a.eps_rows = eps_rows; a.explore_mask = explore_mask; a.explore_action = explore_action;
   a.rng_step = rng_step; a.q = q; a.qmax = qmax; a.action = action;
+  a.hcarry = hcarry; a.carry_in = carry_in ? 1 : 0;
   dim3 grid((B + 15) / 16, a.N);
-  hipLaunchKernelGGL(rdqn_q_kernel, grid, dim3(64), 0, reinterpret_cast<hipStream_t>(stream), a);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (rec && hcarry) hipLaunchKernelGGL((rdqn_q_kernel<true, true>), grid, dim3(64), 0, s, a);
+  else if (rec) hipLaunchKernelGGL((rdqn_q_kernel<true, false>), grid, dim3(64), 0, s, a);
+  else if (hcarry) hipLaunchKernelGGL((rdqn_q_kernel<false, true>), grid, dim3(64), 0, s, a);
+  else hipLaunchKernelGGL((rdqn_q_kernel<false, false>), grid, dim3(64), 0, s, a);
   D2D_CHECK_HIP(hipGetLastError());
   return D2D_OK;
+}
+
+extern "C" int d2d_rdqn_q(const d2d_rdqn_desc* d, const float* obs, const int32_t* samples, int32_t B,
+                          int32_t row_shift, int32_t mode, float eps, const float* eps_rows, int32_t ready,
+                          const uint8_t* explore_mask, const uint8_t* explore_action, uint32_t rng_step, float* q, float* qmax, void* action,
+                          void* stream) {
+  return d2d_rdqn_q_ex(d, obs, D2D_OBS_F32, nullptr, samples, B, row_shift, mode, eps, eps_rows, ready, explore_mask,
+                       explore_action, rng_step, nullptr, 0, q, qmax, action, stream);
 }
 
 extern "C" int64_t d2d_rdqn_grad_workspace(const d2d_rdqn_desc* d, int32_t B, int32_t L) {
@@ -644,12 +747,15 @@ extern "C" int64_t d2d_rdqn_grad_workspace(const d2d_rdqn_desc* d, int32_t B, in
   return ws_layout(d->n_agents, L, B, (d->hidden + 15) / 16, (d->obs_dim + 15) / 16).total;
 }
 
-extern "C" int d2d_rdqn_grad(const d2d_rdqn_desc* d, const float* obs, const int32_t* samples, int32_t B, int32_t L,
-                             const void* action, const float* reward, const uint8_t* done, const float* qmax_target,
-                             float gamma, int32_t loss_kind, float* g_w_ih, float* g_w_hh, float* g_b_ih,
-                             float* g_b_hh, float* g_w1, float* g_b1, float* g_w2, float* g_b2, float* g_w3,
-                             float* g_b3, float* loss, float* workspace, int64_t workspace_floats, void* stream) {
-  int rc = check_desc(d, "d2d_rdqn_grad");
+extern "C" int d2d_rdqn_grad_ex(const d2d_rdqn_desc* d, const void* obs, int32_t obs_format,
+                                const uint32_t* obs_signed, const int32_t* samples, int32_t B, int32_t L,
+                                const void* action, const float* reward, const uint8_t* done,
+                                const float* qmax_target, float gamma, int32_t loss_kind, float* g_w_ih, float* g_w_hh,
+                                float* g_b_ih, float* g_b_hh, float* g_w1, float* g_b1, float* g_w2, float* g_b2,
+                                float* g_w3, float* g_b3, float* loss, float* workspace, int64_t workspace_floats,
+                                void* stream) {
+  const char* fn = "d2d_rdqn_grad";
+  int rc = check_desc(d, fn);
   if (rc) return rc;
   if (L < 1 || L > kMaxWindow) {
     d2d_set_error("d2d_rdqn_grad: supports window lengths in [1, %d] (got %d)", kMaxWindow, L);
@@ -664,6 +770,11 @@ extern "C" int d2d_rdqn_grad(const d2d_rdqn_desc* d, const float* obs, const int
     d2d_set_error("d2d_rdqn_grad: NULL buffer or B < 1");
     return D2D_EINVAL;
   }
+  const float* f32;
+  const uint8_t* rec;
+  const uint32_t* sgn;
+  rc = obs_args(fn, obs_format, obs_signed, d->obs_dim, obs, f32, rec, sgn);
+  if (rc) return rc;
   const WsLayout w = ws_layout(d->n_agents, L, B, (d->hidden + 15) / 16, (d->obs_dim + 15) / 16);
   if (workspace_floats < w.total || !aligned16(workspace)) {
     d2d_set_error("d2d_rdqn_grad: workspace of %lld floats, d2d_rdqn_grad_workspace asks for %lld (16-byte aligned)",
@@ -671,7 +782,7 @@ extern "C" int d2d_rdqn_grad(const d2d_rdqn_desc* d, const float* obs, const int
     return D2D_EINVAL;
   }
   if (d->n_agents == 0) return D2D_OK;
-  RdqnArgs a = make_args(d, obs, samples, B, 0);
+  RdqnArgs a = make_args(d, f32, rec, sgn, samples, B, 0);
   a.L = L; a.ntiles = (B + 15) / 16; a.huber = loss_kind == D2D_RDQN_HUBER; a.gamma = gamma;
   a.act_in = action; a.reward = reward; a.done = done; a.qmax_target = qmax_target;
   a.g_w_ih = g_w_ih; a.g_w_hh = g_w_hh; a.g_b_ih = g_b_ih; a.g_b_hh = g_b_hh; a.g_w1 = g_w1; a.g_b1 = g_b1;
@@ -680,9 +791,20 @@ extern "C" int d2d_rdqn_grad(const d2d_rdqn_desc* d, const float* obs, const int
   a.ws_y2 = workspace + w.y2; a.ws_d1 = workspace + w.d1; a.ws_d2 = workspace + w.d2; a.ws_dq = workspace + w.dq;
   a.ws_loss = workspace + w.loss;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(rdqn_bptt_kernel, dim3(a.ntiles, a.N), dim3(64), 0, s, a);
+  if (rec) hipLaunchKernelGGL(rdqn_bptt_kernel<true>, dim3(a.ntiles, a.N), dim3(64), 0, s, a);
+  else hipLaunchKernelGGL(rdqn_bptt_kernel<false>, dim3(a.ntiles, a.N), dim3(64), 0, s, a);
   D2D_CHECK_HIP(hipGetLastError());
   hipLaunchKernelGGL(rdqn_wgrad_kernel, dim3(wgrad_tiles(a.HT, a.IT), a.N), dim3(64), 0, s, a);
   D2D_CHECK_HIP(hipGetLastError());
   return D2D_OK;
+}
+
+extern "C" int d2d_rdqn_grad(const d2d_rdqn_desc* d, const float* obs, const int32_t* samples, int32_t B, int32_t L,
+                             const void* action, const float* reward, const uint8_t* done, const float* qmax_target,
+                             float gamma, int32_t loss_kind, float* g_w_ih, float* g_w_hh, float* g_b_ih,
+                             float* g_b_hh, float* g_w1, float* g_b1, float* g_w2, float* g_b2, float* g_w3,
+                             float* g_b3, float* loss, float* workspace, int64_t workspace_floats, void* stream) {
+  return d2d_rdqn_grad_ex(d, obs, D2D_OBS_F32, nullptr, samples, B, L, action, reward, done, qmax_target, gamma,
+                          loss_kind, g_w_ih, g_w_hh, g_b_ih, g_b_hh, g_w1, g_b1, g_w2, g_b2, g_w3, g_b3, loss, workspace,
+                          workspace_floats, stream);
 }

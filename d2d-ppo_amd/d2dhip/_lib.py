@@ -191,6 +191,13 @@ _SIGS = {
     "d2d_rdqn_grad_workspace": (ctypes.c_int64, [ctypes.POINTER(RdqnDesc), ctypes.c_int32, ctypes.c_int32]),
     "d2d_rdqn_grad": (ctypes.c_int, [ctypes.POINTER(RdqnDesc), _p, _p, ctypes.c_int32, ctypes.c_int32, _p, _p, _p, _p,
                                       ctypes.c_float, ctypes.c_int32] + [_p] * 12 + [ctypes.c_int64, _p]),
+    "d2d_rdqn_carry_floats": (ctypes.c_int64, [ctypes.POINTER(RdqnDesc), ctypes.c_int32]),
+    "d2d_rdqn_q_ex": (ctypes.c_int, [ctypes.POINTER(RdqnDesc), _p, ctypes.c_int32, _p, _p, ctypes.c_int32,
+                                      ctypes.c_int32, ctypes.c_int32, ctypes.c_float, _p, ctypes.c_int32, _p, _p,
+                                      ctypes.c_uint32, _p, ctypes.c_int32, _p, _p, _p, _p]),
+    "d2d_rdqn_grad_ex": (ctypes.c_int, [ctypes.POINTER(RdqnDesc), _p, ctypes.c_int32, _p, _p, ctypes.c_int32,
+                                         ctypes.c_int32, _p, _p, _p, _p, ctypes.c_float, ctypes.c_int32] + [_p] * 12
+                         + [ctypes.c_int64, _p]),
     "d2d_last_error": (ctypes.c_char_p, []),
     "d2d_abi_version": (ctypes.c_int, []),
 }

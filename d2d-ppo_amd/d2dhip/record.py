@@ -98,6 +98,43 @@ class ObsRecord:
         return torch.where(neg, s, u)
 
 
+def _signed_columns(signed, obs_dim):
+    """bool [N][F]: which columns of agent k's row are int8."""
+    sg = signed.to(torch.int64) & 0xFFFFFFFF
+    cols = torch.arange(obs_dim, device=signed.device)
+    return ((sg[:, cols // 32] >> (cols % 32)) & 1).bool()
+
+
+def encode(obs_f32, signed, out=None):
+    """The inverse of ObsRecord.decode, on the host or the device: integer-valued float32 rows [..., N, F] as an
+    ObsRecord (into `out`, an ObsRecord of the same logical shape, or a new one on obs_f32's device) -- bytes
+    [0, F) the values (int8 on the columns `signed` marks, int32 [N][R / 32]), byte F the bias input 1, zeros after
+    it.  ValueError when a value is not an integer or outside its column's uint8 / int8 range."""
+    if obs_f32.dtype != torch.float32 or obs_f32.dim() < 2:
+        raise ValueError("encode takes float32 rows [..., N, F]")
+    N, F = obs_f32.shape[-2:]
+    R = _lib.record_bytes(F)
+    signed = signed.to(obs_f32.device)
+    if signed.dtype != torch.int32 or tuple(signed.shape) != (N, R // 32):
+        raise ValueError(f"signed masks must be int32 [{N}][{R // 32}]")
+    neg = _signed_columns(signed, F)                                  # [N][F]
+    lo = torch.where(neg, -128.0, 0.0)
+    hi = torch.where(neg, 127.0, 255.0)
+    bad = (obs_f32 != obs_f32.round()) | (obs_f32 < lo) | (obs_f32 > hi) | ~torch.isfinite(obs_f32)
+    if bool(bad.any()):
+        v = obs_f32[bad][0].item()
+        raise ValueError(f"the obs record holds integers in [0, 255] (int8 columns [-128, 127]); got {v}")
+    if out is None:
+        out = ObsRecord(torch.zeros(tuple(obs_f32.shape[:-1]) + (R,), dtype=torch.uint8, device=obs_f32.device), F,
+                        signed)
+    elif not isinstance(out, ObsRecord) or out.shape != tuple(obs_f32.shape):
+        raise ValueError(f"out must be an ObsRecord of logical shape {tuple(obs_f32.shape)}")
+    out.data[..., :F] = obs_f32.to(torch.int16).to(torch.uint8)       # two's complement: int8 b -> b & 0xFF
+    out.data[..., F] = 1
+    out.data[..., F + 1:] = 0
+    return out
+
+
 def obs_arg(obs):
     """(device pointer, obs_format, obs_signed pointer) of an fp32 obs tensor or an ObsRecord."""
     if isinstance(obs, ObsRecord):

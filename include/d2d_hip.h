@@ -54,7 +54,8 @@ extern "C" {
                               15: actions = NULL in forced mode (d2d_policy_mlp_step, d2d_policy_gru);
                               still 15, additive: d2d_rdqn_q, d2d_rdqn_grad, d2d_rdqn_grad_workspace (iRDQN);
                               still 15, additive: d2d_env_packed_state, d2d_env_reset_packed, d2d_env_step_packed,
-                              d2d_env_state_pack, d2d_env_state_unpack (no layout change) */
+                              d2d_env_state_pack, d2d_env_state_unpack (no layout change);
+                              still 15, additive: d2d_rdqn_q_ex, d2d_rdqn_grad_ex, d2d_rdqn_carry_floats */
 
 enum { D2D_ENV_COMBINATORIAL = 0, D2D_ENV_CHANNEL_SELECTION = 1, D2D_ENV_SINGLE = 2 };
 enum { D2D_ARRIVAL_POISSON = 0, D2D_ARRIVAL_SCHEDULED_BERNOULLI = 1, D2D_ARRIVAL_NONE = 2 };
@@ -551,6 +552,35 @@ int d2d_rdqn_grad(const d2d_rdqn_desc* desc, const float* obs, const int32_t* sa
                   int32_t loss_kind, float* g_w_ih, float* g_w_hh, float* g_b_ih, float* g_b_hh, float* g_w1,
                   float* g_b1, float* g_w2, float* g_b2, float* g_w3, float* g_b3, float* loss, float* workspace,
                   int64_t workspace_floats, void* stream);
+
+/* The same two calls on either obs format, and an acting state carried from slot to slot (additive, ABI 15;
+ * d2d_rdqn_q / d2d_rdqn_grad are these with D2D_OBS_F32, no obs_signed and no hcarry).
+ * obs_format D2D_OBS_F32: obs is the fp32 ring above.  D2D_OBS_U8: obs is the env kernel's compact record
+ * uint8 [ring_rows][n_envs][N][D2D_RECORD_BYTES(obs_dim)] (16-byte aligned) -- the replay memory of iRDQN.train's
+ * ReplayBuffer (irdqn.py:15-48) at 32 bytes per agent row instead of 4 obs_dim -- and obs_signed (device uint32
+ * [N][D2D_RECORD_BYTES(obs_dim) / 32], as in d2d_mlp_desc) marks agent k's int8 columns.  Only bytes [0, obs_dim) of a
+ * row are read as inputs: byte obs_dim (the MLP kernels' bias input) and the bytes after it are ignored, so every
+ * result is bit-identical to the fp32 ring of the decoded rows.
+ * hcarry (optional): d2d_rdqn_carry_floats(desc, B) floats of device scratch, 16-byte aligned, layout private to the
+ * library.  When given, the call leaves every sample's final hidden state there.  carry_in != 0 (the acting loop of
+ * iRDQN.train, irdqn.py:242-265, while the window is still an episode prefix): h0 is read from hcarry and exactly ONE
+ * GRU step runs per sample, on row samples[b].last, instead of the whole window -- the same arithmetic as the
+ * recompute, bit for bit.  Contract of carry_in: the previous call on this hcarry had the same desc shapes and
+ * parameter VALUES, the same B and sample <-> env mapping, last - 1 and window length - 1 for every sample, and
+ * row_shift 0.  The samples live on the device, so the library cannot verify this; d2dhip.rdqn.CarryState does.
+ * D2D_EINVAL: unknown obs_format, D2D_OBS_U8 without obs_signed or with a misaligned obs, carry_in without hcarry or
+ * with row_shift != 0, a misaligned hcarry.  d2d_rdqn_carry_floats returns -1 for a bad desc or B. */
+int64_t d2d_rdqn_carry_floats(const d2d_rdqn_desc* desc, int32_t B);
+int d2d_rdqn_q_ex(const d2d_rdqn_desc* desc, const void* obs, int32_t obs_format, const uint32_t* obs_signed,
+                  const int32_t* samples, int32_t B, int32_t row_shift, int32_t mode, float eps,
+                  const float* eps_rows, int32_t ready, const uint8_t* explore_mask, const uint8_t* explore_action,
+                  uint32_t rng_step, float* hcarry, int32_t carry_in, float* q, float* qmax, void* action,
+                  void* stream);
+int d2d_rdqn_grad_ex(const d2d_rdqn_desc* desc, const void* obs, int32_t obs_format, const uint32_t* obs_signed,
+                     const int32_t* samples, int32_t B, int32_t L, const void* action, const float* reward,
+                     const uint8_t* done, const float* qmax_target, float gamma, int32_t loss_kind, float* g_w_ih,
+                     float* g_w_hh, float* g_b_ih, float* g_b_hh, float* g_w1, float* g_b1, float* g_w2, float* g_b2,
+                     float* g_w3, float* g_b3, float* loss, float* workspace, int64_t workspace_floats, void* stream);
 
 /* Process-wide tuning options (not part of the reference interface).
  * D2D_OPT_NT_STORES: 1 = write obs/state with non-temporal (streaming) stores.  Default: 0.
