@@ -20,6 +20,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 
 #include "common.h"
 #include "policy_split.h"
@@ -30,7 +31,11 @@ constexpr int kBlock = 256;
 // comb_kernel register budget and the lane count of a record-only step (no LDS staging): 7 waves
 // per SIMD (<= 72 VGPRs, no spills; unhinted the allocator takes 91 and runs 5) in 256-lane blocks
 // (512-lane blocks would fit only 3 per SIMD pair of waves): record step 68.5 -> 64.9 us at
-// 64 x 8 x 65,536; 8 waves spill (76 us).
+// 64 x 8 x 65,536; 8 waves spill (76 us).  Tried again with the wave-per-env step: at 7 waves its headline kernel
+// has 65 VGPRs, no scratch and 27 SGPRs spilled to VGPR lanes, of which every wave of the record-only step runs
+// 12 v_writelane and 20 v_readlane (8 argument words parked at entry and read back for the reward and at the
+// end, two saved lane masks); at 8 waves the kernel runs 54.1 -> 52.4 us but spills a VGPR to scratch (8 B per
+// lane) and 48 SGPRs.  Neither is spill-free; 7 stays because it keeps the step kernel out of scratch.
 constexpr int kCombWavesPerEu = 7;
 constexpr int kCombRecBlock = 256;
 constexpr int kMaxAgents = 1024;
@@ -270,6 +275,22 @@ __device__ __forceinline__ Lane lane_geometry(const EnvArgs& a, int bidx = block
   return L;
 }
 
+// One env per wave (33-64 agents, a.seg == 64): the wave and env indices go through readfirstlane, so the
+// compiler can prove them wave-uniform and keeps the env's addresses, ballots, counts and acks in scalar
+// registers; the segment mask is the constant all-ones and folds away.  L.active is k < N alone: the caller
+// retires a wave whose env is >= E before it reads or writes anything.
+__device__ __forceinline__ Lane wave_geometry(const EnvArgs& a, int bidx) {
+  Lane L;
+  L.lane = threadIdx.x & (kWave - 1);
+  L.k = L.lane;
+  L.envs_per_block = blockDim.x >> 6;
+  L.local_env = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  L.env = __builtin_amdgcn_readfirstlane(bidx * L.envs_per_block + L.local_env);
+  L.segmask = ~0ull;
+  L.active = L.k < a.N;
+  return L;
+}
+
 // Sum of `v` over the lanes of this lane's env (segment ballot or LDS).
 template <bool LARGE>
 __device__ __forceinline__ int env_count(bool v, const Lane& L, int* lds_acc) {
@@ -340,6 +361,9 @@ __device__ __forceinline__ void flush_bf16(uint16_t* __restrict__ dst, const flo
 //           the top sizeof(MaskT) bytes of the last word (max_deadline + mask bytes <= 4 DW, checked by the
 //           host), a.recv one counter word per agent, received in the low and discarded in the high half;
 //           a.chan and a.disc are not touched.  Only the state load and the state store differ.
+//   WAVE  : 33-64 agents, the env is the whole wave (wave_geometry): scalar env index, addresses, channel
+//           counts and acks, Philox with the wave-uniform head (philox_head_of), the record's ack words built
+//           once per wave.  The step with uint8 masks; same results bit for bit.
 // LDS: [cnt_words][per-wave obs slots: 64*F floats each][state]
 //   N <= 64 : state staged per wave (the wave's envs), flushed by the wave;
 //   N  > 64 : state of the block's single env staged per block.
@@ -348,20 +372,28 @@ __device__ __forceinline__ void flush_bf16(uint16_t* __restrict__ dst, const flo
 // (bidx = blockIdx.x); the fused env + policy slot (comb_policy_fused_kernel) runs it for the consecutive
 // env groups of its slice and passes lrec, an LDS image of the slice's records (agent k's row of env e at
 // lrec[k * lstride + 2 (e - lenv0)], two 16-byte words) that the slot's policy then reads instead of HBM.
-template <typename MaskT, int DW, bool LARGE, int CT, bool RESET, bool PACKED = false>
+template <typename MaskT, int DW, bool LARGE, int CT, bool RESET, bool PACKED = false, bool WAVE = false>
 __device__ __forceinline__ void comb_step(const EnvArgs a, float* lds, int bidx, uint4* lrec, int lstride, int lenv0) {
-  const Lane L = lane_geometry<LARGE>(a, bidx);
+  static_assert(!WAVE || (!LARGE && !RESET && sizeof(MaskT) == 1), "the wave-per-env path: uint8 masks, N <= 64, the step");
+  const Lane L = WAVE ? wave_geometry(a, bidx) : lane_geometry<LARGE>(a, bidx);
+  if constexpr (WAVE) {
+    if (L.env >= a.E) return;  // an idle wave of a ragged last block (no workgroup barrier follows)
+  }
   const int N = a.N, F = a.F;
   const int C = CT ? CT : a.C;
-  const int wave = threadIdx.x >> 6;
+  const int wave = WAVE ? L.local_env : (int)(threadIdx.x >> 6);
   const int nwaves = blockDim.x >> 6;
   int* cnt = reinterpret_cast<int*>(lds);  // LARGE: n[32], g[32]; reward at [64]
   const int slot = (kWave * F + 3) & ~3;
   float* lds_obs = lds + a.cnt_words + wave * slot;
-  const int epw = LARGE ? 1 : kWave / a.seg;  // envs per wave
+  const int epw = (LARGE || WAVE) ? 1 : kWave / a.seg;  // envs per wave
   float* lds_state = LARGE ? lds + a.cnt_words + nwaves * slot
                            : lds + a.cnt_words + nwaves * slot + wave * ((epw * a.S + 3) & ~3);
   const size_t row = (size_t)L.env * N + L.k;
+  // the agent's element of a per-agent array: WAVE, the env's scalar base plus a 32-bit lane offset
+  const size_t row0 = WAVE ? (size_t)L.env * N : row;
+  const uint32_t ko = WAVE ? (uint32_t)L.k : 0u;
+  auto at = [&](auto* base, uint32_t per) { return base + row0 * per + (uint32_t)(ko * per); };
   const uint64_t genv = a.env_base + (uint64_t)L.env;
   const uint32_t cmask = (C >= 32) ? 0xFFFFFFFFu : ((1u << C) - 1u);
   // PACKED: the mask's place in the last row word
@@ -373,25 +405,46 @@ __device__ __forceinline__ void comb_step(const EnvArgs a, float* lds, int bidx,
   for (int i = 0; i < DW; ++i) b.w[i] = 0;
   uint32_t h_pre = cmask, act = 0, rc = 0, dc = 0;
   d2d_agent_entry ag{};
+  // WAVE: the Philox draws of the step need none of the loaded state.  The head (rounds 1-3, mostly scalar) is
+  // shared by the flip and arrival blocks; the arrival block runs only where the draw mask names a lane of
+  // this wave and no recorded arrivals replace it.
+  constexpr int kWaveFlipBlocks = 2;  // uint8 masks: C <= 8
+  philox_head ph{};
+  u32x4 flip_r[kWaveFlipBlocks] = {};
+  uint32_t arr_r = 0;
+  const bool wave_draws = WAVE && !a.arrivals && (a.draw[0] & (N >= kWave ? ~0ull : ((1ull << N) - 1ull))) != 0;
+  auto wave_philox = [&]() {
+    if (a.flips && !wave_draws) return;
+    ph = philox_head_of((uint32_t)genv, (uint32_t)L.k, rng_of(a), a.seed);
+    if (!a.flips) {
+#pragma unroll
+      for (int blk = 0; blk < kWaveFlipBlocks; ++blk)
+        if (blk * 4 < C) flip_r[blk] = philox_tail(ph, (kStreamFlip << 24) | (uint32_t)blk, a.seed);
+    }
+    if (wave_draws) arr_r = philox_tail(ph, kStreamArrival << 24, a.seed).x;
+  };
   if (L.active) {
     ag = a.agents[L.k];
     if (!RESET) {
-      load_row<DW>(b, a.buf + row * DW);
-      act = (uint32_t)reinterpret_cast<const MaskT*>(a.actions)[row] & cmask;
+      load_row<DW>(b, at(a.buf, DW));
+      act = (uint32_t)*at(reinterpret_cast<const MaskT*>(a.actions), 1) & cmask;
       if constexpr (PACKED) {
         // the mask out of the top bytes of the last word; those bytes are zero in the register row, as
         // row_any, the record's word-level build, row_byte and the state output expect
         h_pre = (b.w[DW - 1] >> kMaskShift) & cmask;
         b.w[DW - 1] &= kRowKeep;
-        const uint32_t cw = a.recv[row];
+        const uint32_t cw = *at(a.recv, 1);
         rc = cw & 0xFFFFu;
         dc = cw >> 16;
       } else {
-        h_pre = (uint32_t)reinterpret_cast<const MaskT*>(a.chan)[row] & cmask;
-        rc = a.recv[row];
-        dc = a.disc[row];
+        h_pre = (uint32_t)*at(reinterpret_cast<const MaskT*>(a.chan), 1) & cmask;
+        rc = *at(a.recv, 1);
+        dc = *at(a.disc, 1);
       }
     }
+    // right after the loads are issued, ahead of their first use (the channel counts): kernel 54.8 -> 54.1 us
+    // at 64 x 8 x 65,536 against drawing where the flips are applied
+    if constexpr (WAVE) wave_philox();
   }
   if (LARGE) {
     if (threadIdx.x < 80) cnt[threadIdx.x] = 0;
@@ -425,6 +478,12 @@ __device__ __forceinline__ void comb_step(const EnvArgs a, float* lds, int bidx,
     } else {
       for (int c = 0; c < C; ++c) count_channel(c);
     }
+    if constexpr (WAVE) {
+      // the two ack masks as scalar words from here on: without this the compiler carries the per-channel
+      // conditions they were built from (2 C scalar register pairs) to every later use and spills them
+      ack_one = __builtin_amdgcn_readfirstlane(ack_one);
+      ack_zero = __builtin_amdgcn_readfirstlane(ack_zero);
+    }
     if (LARGE) {
       __syncthreads();
       for (int c = 0; c < C; ++c) {
@@ -442,7 +501,17 @@ __device__ __forceinline__ void comb_step(const EnvArgs a, float* lds, int bidx,
     uint32_t f = 0;
     if (L.active) {
       if (a.flips) {
-        f = (uint32_t)reinterpret_cast<const MaskT*>(a.flips)[row];
+        f = (uint32_t)*at(reinterpret_cast<const MaskT*>(a.flips), 1);
+      } else if constexpr (WAVE) {
+        const uint64_t* thr = a.flip_thr + (uint32_t)(L.k * C);
+#pragma unroll
+        for (int blk = 0; blk < kWaveFlipBlocks; ++blk) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const int c = blk * 4 + i;
+            if (c < C) f |= (uint32_t)((uint64_t)pick(flip_r[blk], i) < thr[c]) << c;
+          }
+        }
       } else {
         const uint64_t* thr = a.flip_thr + (size_t)L.k * C;
         auto flip_block = [&](int blk) {
@@ -466,7 +535,14 @@ __device__ __forceinline__ void comb_step(const EnvArgs a, float* lds, int bidx,
   // arrivals (reset 66-85, step 178-196); N <= 64 keeps the draw mask in one word
   const bool drew = L.active && (LARGE ? draws_now(a, L.k) : ((a.draw[0] >> L.k) & 1ull));
   if (drew) {
-    const uint32_t x = arrival_value(a, ag, row, L.k, genv);
+    uint32_t x;
+    if constexpr (WAVE) {  // arrival_value() on the wave's Philox word
+      if (a.arrivals) x = *at(a.arrivals, 1);
+      else if (ag.arrival_kind == D2D_ARRIVAL_POISSON) x = poisson_lookup(arr_r, a.pois_cdf + (uint32_t)(L.k * 256));
+      else x = (uint64_t)arr_r < ag.arrival_thr ? 1u : 0u;
+    } else {
+      x = arrival_value(a, ag, row, L.k, genv);
+    }
     row_set<DW>(b, (int)ag.deadline - 1, x);
     rc = (RESET ? 0u : rc) + x;
   } else if (RESET) {
@@ -478,16 +554,16 @@ __device__ __forceinline__ void comb_step(const EnvArgs a, float* lds, int bidx,
     if constexpr (PACKED) {
       Row<DW> o = b;
       o.w[DW - 1] |= h_new << kMaskShift;
-      store_row<DW>(o, a.buf + row * DW);
-      a.recv[row] = rc | (dc << 16);  // both below 65,536 (the caller's bound, d2d_env_step_packed)
+      store_row<DW>(o, at(a.buf, DW));
+      *at(a.recv, 1) = rc | (dc << 16);  // both below 65,536 (the caller's bound, d2d_env_step_packed)
     } else {
-      store_row<DW>(b, a.buf + row * DW);
-      reinterpret_cast<MaskT*>(a.chan)[row] = (MaskT)h_new;
-      a.recv[row] = rc;
-      a.disc[row] = dc;
+      store_row<DW>(b, at(a.buf, DW));
+      *at(reinterpret_cast<MaskT*>(a.chan), 1) = (MaskT)h_new;
+      *at(a.recv, 1) = rc;
+      *at(a.disc, 1) = dc;
     }
     if (!RESET) {
-      if (a.success) a.success[row] = succ ? 1 : 0;
+      if (a.success) *at(a.success, 1) = succ ? 1 : 0;
       if (L.k == 0) {
         if (a.reward) a.reward[L.env] = nsucc;  // rewards = len(successful_users) (211)
         if (a.ack) {
@@ -546,7 +622,7 @@ __device__ __forceinline__ void comb_step(const EnvArgs a, float* lds, int bidx,
       if (c < C) return ((ack_one >> c) & 1u) | (((ack_neg >> c) & 1u) * 0xFFu);
       return p == F ? 1u : 0u;
     };
-    uint4* dst = reinterpret_cast<uint4*>(a.rec + row * (size_t)a.rec_bytes);
+    uint4* dst = reinterpret_cast<uint4*>(at(a.rec, (uint32_t)a.rec_bytes));
     uint32_t v[8];
     bool built = false;
     if constexpr (CT != 0 && 2 * CT <= 16 && 4 * DW <= 16) {
@@ -563,29 +639,71 @@ __device__ __forceinline__ void comb_step(const EnvArgs a, float* lds, int bidx,
           blk[u] = expand4((h_pre >> (4 * u)) & 0xFu);
           blk[CT / 4 + u] = expand4((ack_one >> (4 * u)) & 0xFu) | expand4((ack_neg >> (4 * u)) & 0xFu) * 0xFFu;
         }
-        const int ws = w >> 2, bs = w & 3;
-        uint32_t sh[NB + 1];  // the block shifted up by bs bytes
-#pragma unroll
-        for (int j = 0; j <= NB; ++j) {
-          const uint32_t hi = j < NB ? blk[j] : 0u, lo = j > 0 ? blk[j - 1] : 0u;
-          sh[j] = bs == 0 ? hi : __builtin_amdgcn_alignbyte(hi, lo, 4 - bs);
-        }
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          uint32_t word = q < DW ? b.w[q < DW ? q : 0] : 0u;
-#pragma unroll
-          for (int c = 0; c <= 16 / 4; ++c)  // w_k <= 4 DW <= 16: word shift 0 .. 4
-            if (q - c >= 0 && q - c <= NB) word |= ws == c ? sh[q - c] : 0u;
-          word |= (q == (F >> 2)) ? (1u << (8 * (F & 3))) : 0u;
-          v[q] = word;
-        }
         const bool nt = a.flags & 1u;
-        st_rec(dst, v[0], v[1], v[2], v[3], nt);
-        st_rec(dst + 1, v[4], v[5], v[6], v[7], nt);
-        if (lrec) {
-          uint4* l = lrec + (size_t)L.k * lstride + 2 * (L.env - lenv0);
-          l[0] = make_uint4(v[0], v[1], v[2], v[3]);
-          l[1] = make_uint4(v[4], v[5], v[6], v[7]);
+        // WAVE: the ack words above are scalar.  Where every agent of the env has the same w_k (always so
+        // with homogeneous_size; the host keeps no copy of the agent table, so the wave compares against its
+        // first lane's), the byte shift is a scalar amount, the all-ack words shift on the scalar unit, and
+        // the word shift is a scalar branch to code with the words in fixed places.
+        bool placed = false;
+        if constexpr (WAVE) {
+          const int w0 = __builtin_amdgcn_readfirstlane(w);
+          if (__ballot(w != w0) == 0) {
+            const int ws = w0 >> 2, bs = w0 & 3;
+            uint32_t sh[NB + 1];
+#pragma unroll
+            for (int j = 0; j <= NB; ++j) {
+              const uint32_t hi = j < NB ? blk[j] : 0u, lo = j > 0 ? blk[j - 1] : 0u;
+              if (j > CT / 4)  // both words are acks (or zero): a scalar 64-bit shift
+                sh[j] = (uint32_t)((((uint64_t)hi << 32) | lo) >> (32 - 8 * bs));
+              else
+                sh[j] = bs == 0 ? hi : __builtin_amdgcn_alignbyte(hi, lo, 4 - bs);
+            }
+            auto place = [&](auto shift) {
+              constexpr int c = decltype(shift)::value;
+#pragma unroll
+              for (int q = 0; q < 8; ++q) {
+                uint32_t word = q < DW ? b.w[q < DW ? q : 0] : 0u;
+                if (q - c >= 0 && q - c <= NB) word |= sh[q - c >= 0 && q - c <= NB ? q - c : 0];
+                word |= (q == (F >> 2)) ? (1u << (8 * (F & 3))) : 0u;
+                v[q] = word;
+              }
+              st_rec(dst, v[0], v[1], v[2], v[3], nt);
+              st_rec(dst + 1, v[4], v[5], v[6], v[7], nt);
+            };
+            switch (ws) {  // w_k <= 4 DW <= 16: word shift 0 .. 4
+              case 0: place(std::integral_constant<int, 0>{}); break;
+              case 1: place(std::integral_constant<int, 1>{}); break;
+              case 2: place(std::integral_constant<int, 2>{}); break;
+              case 3: place(std::integral_constant<int, 3>{}); break;
+              default: place(std::integral_constant<int, 4>{}); break;
+            }
+            placed = true;
+          }
+        }
+        if (!placed) {
+          const int ws = w >> 2, bs = w & 3;
+          uint32_t sh[NB + 1];  // the block shifted up by bs bytes
+#pragma unroll
+          for (int j = 0; j <= NB; ++j) {
+            const uint32_t hi = j < NB ? blk[j] : 0u, lo = j > 0 ? blk[j - 1] : 0u;
+            sh[j] = bs == 0 ? hi : __builtin_amdgcn_alignbyte(hi, lo, 4 - bs);
+          }
+#pragma unroll
+          for (int q = 0; q < 8; ++q) {
+            uint32_t word = q < DW ? b.w[q < DW ? q : 0] : 0u;
+#pragma unroll
+            for (int c = 0; c <= 16 / 4; ++c)  // w_k <= 4 DW <= 16: word shift 0 .. 4
+              if (q - c >= 0 && q - c <= NB) word |= ws == c ? sh[q - c] : 0u;
+            word |= (q == (F >> 2)) ? (1u << (8 * (F & 3))) : 0u;
+            v[q] = word;
+          }
+          st_rec(dst, v[0], v[1], v[2], v[3], nt);
+          st_rec(dst + 1, v[4], v[5], v[6], v[7], nt);
+          if (lrec) {
+            uint4* l = lrec + (size_t)L.k * lstride + 2 * (L.env - lenv0);
+            l[0] = make_uint4(v[0], v[1], v[2], v[3]);
+            l[1] = make_uint4(v[4], v[5], v[6], v[7]);
+          }
         }
         built = true;
       }
@@ -653,10 +771,10 @@ __device__ __forceinline__ void comb_step(const EnvArgs a, float* lds, int bidx,
   }
 }
 
-template <typename MaskT, int DW, bool LARGE, int CT, bool RESET, bool PACKED = false>
+template <typename MaskT, int DW, bool LARGE, int CT, bool RESET, bool PACKED = false, bool WAVE = false>
 __global__ __launch_bounds__(kMaxAgents) __attribute__((amdgpu_waves_per_eu(kCombWavesPerEu))) void comb_kernel(EnvArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  comb_step<MaskT, DW, LARGE, CT, RESET, PACKED>(a, lds, blockIdx.x, nullptr, 0, 0);
+  comb_step<MaskT, DW, LARGE, CT, RESET, PACKED, WAVE>(a, lds, blockIdx.x, nullptr, 0, 0);
 }
 
 // =====================================================================
@@ -1237,6 +1355,12 @@ int launch(K kernel, const EnvArgs& a, int block, hipStream_t s, int kind) {
 template <typename MaskT, int DW, int CT, bool RESET, bool PACKED = false>
 int dispatch_comb_ct(const EnvArgs& a, int block, hipStream_t s) {
   if (a.N > kWave) return launch(comb_kernel<MaskT, DW, true, CT, RESET, PACKED>, a, block, s, D2D_ENV_COMBINATORIAL);
+  // 33-64 agents: the env is the whole wave, the wave-per-env instantiation (wave_geometry).  The step with
+  // uint8 masks only (every CT, packed or not): resets and the uint16 / uint32 masks of C > 8 stay on the
+  // segment path, as does the fused slot
+  if constexpr (!RESET && sizeof(MaskT) == 1) {
+    if (a.seg == kWave) return launch(comb_kernel<MaskT, DW, false, CT, RESET, PACKED, true>, a, block, s, D2D_ENV_COMBINATORIAL);
+  }
   return launch(comb_kernel<MaskT, DW, false, CT, RESET, PACKED>, a, block, s, D2D_ENV_COMBINATORIAL);
 }
 
