@@ -142,12 +142,15 @@ class BatchedLearnerBase(DataParallelMixin):
         return self._fused
 
     def _gru_ok(self):
-        """The GRU window-policy kernels (csrc/gru_kernels.hip) cover the RNN learners with H <= 64,
-        A <= 16 and F + 1 <= 64 inputs (up to four 16-column input tiles: xp_load's 30 inputs and
-        run_ippo_combinatorial.py's 6 x 16-channel env with 14 + 2 * 16 = 46)."""
+        """The GRU window-policy kernels cover the RNN learners with H <= 128 -- the learners' own default
+        hidden_size and the RNN module's 100 included -- A <= 16 and F + 1 <= 64 inputs (xp_load's 30 inputs and
+        run_ippo_combinatorial.py's 6 x 16-channel env with 14 + 2 * 16 = 46): csrc/gru_kernels.hip up to H = 64
+        (weights in LDS, vectors in registers), csrc/gru_wide_kernels.hip for 65..128 (weights from L2, vectors in
+        LDS; history_len <= 256).  The C ABI picks the file by the hidden size; nothing else here depends on it."""
         if getattr(self, "_gru", None) is None:
             p = self.policy
-            self._gru = (self.useRNN and p.kind == "rnn" and p.H <= 64 and p.A <= 16 and p.F + 1 <= 64
+            self._gru = (self.useRNN and p.kind == "rnn" and p.A <= 16 and p.F + 1 <= 64
+                         and (p.H <= 64 or (p.H <= 128 and self.history_len <= 256))
                          and (self.kind == "comb") == bool(self.combinatorial)
                          and os.environ.get("D2D_FUSED_POLICY", "1") != "0")
         return self._gru
@@ -170,8 +173,8 @@ class BatchedLearnerBase(DataParallelMixin):
 
     def _fused_update_ok(self):
         """The fused HIP update kernels cover the MLP actors with F + 1 <= 64 inputs (and the iPPO
-        per-agent MLP critics; csrc/update_kernels.hip) and the GRU policies / critics
-        (csrc/gru_kernels.hip)."""
+        per-agent MLP critics; csrc/update_kernels.hip) and the GRU policies / critics up to H = 128
+        (csrc/gru_kernels.hip, csrc/gru_wide_kernels.hip: see _gru_ok)."""
         if getattr(self, "_fused_upd", None) is None:
             self._fused_upd = (((self._fused_ok() and self.policy.F + 1 <= 64) or self._gru_ok())
                                and (self.kind == "comb") == bool(self.combinatorial)

@@ -22,6 +22,7 @@
 #include <cmath>
 
 #include "gru_common.h"
+#include "gru_wide.h"
 #include "policy_epilogue.h"
 #include "ppo_epilogue.h"
 
@@ -1393,7 +1394,7 @@ static int check_gru_desc(const d2d_gru_desc* d, const void* obs) {
     return D2D_EINVAL;
   }
   if (d->n_agents < 0 || d->n_envs < 0) { d2d_set_error("negative size"); return D2D_EINVAL; }
-  if (d->hidden < 1 || d->hidden > 64) { d2d_set_error("hidden=%d outside [1,64]", d->hidden); return D2D_EUNSUPPORTED; }
+  if (d->hidden < 1 || d->hidden > kGruWideHidden) { d2d_set_error("hidden=%d outside [1,%d]", d->hidden, kGruWideHidden); return D2D_EUNSUPPORTED; }
   if (d->obs_dim < 1 || d->obs_dim + 1 > 64) { d2d_set_error("obs_dim=%d outside [1,63]", d->obs_dim); return D2D_EUNSUPPORTED; }
   if (d->kind < 0 || d->kind > 2) { d2d_set_error("kind=%d outside [0,2]", d->kind); return D2D_EINVAL; }
   if (d->kind != 2 && (d->n_out < 1 || d->n_out > 16)) { d2d_set_error("n_out=%d outside [1,16]", d->n_out); return D2D_EUNSUPPORTED; }
@@ -1429,6 +1430,7 @@ static int policy_gru(const d2d_gru_desc* d, int32_t T, const void* obs, int32_t
                       float* out, float* hcarry, int32_t carry_in, void* stream);
 
 extern "C" int64_t d2d_gru_carry_floats(const d2d_gru_desc* d) {
+  if (d && d->hidden > kGruNarrowHidden) return gru_wide_carry_floats(d);  // gru_wide_kernels.hip
   if (!d || d->n_agents < 0 || d->n_envs < 0 || d->hidden < 1 || d->hidden > 64) return -1;
   const int64_t ht = (d->hidden + 15) / 16;
   return (int64_t)d->n_agents * ((d->n_envs + 15) / 16) * 4 * (ht <= 1 ? 1 : ht <= 2 ? 2 : 4) * 64;
@@ -1472,6 +1474,9 @@ static int policy_gru(const d2d_gru_desc* d, int32_t T, const void* obs, int32_t
     d2d_set_error("d2d_policy_gru: buffer is not whole episodes");
     return D2D_EINVAL;
   }
+  if (d->hidden > kGruNarrowHidden)  // 65..128: the L2-resident layout of gru_wide_kernels.hip
+    return gru_wide_policy(d, T, obs, slot0, n_slots, padded, forced, rng_step, deterministic, actions, out, hcarry,
+                           carry_in, stream);
   GruArgs a = make_gru_args(d, T, obs);
   a.slot0 = slot0; a.n_slots = n_slots; a.padded = padded ? 1 : 0;
   a.hcarry = hcarry; a.carry_in = carry_in;
@@ -1575,6 +1580,7 @@ static int64_t gru_grad_workspace(const d2d_gru_desc* d, int32_t T, bool history
 }
 
 extern "C" int64_t d2d_gru_grad_workspace(const d2d_gru_desc* d, int32_t T) {
+  if (d && d->hidden > kGruNarrowHidden) return gru_wide_grad_workspace(d, T);  // gru_wide_kernels.hip
   return gru_grad_workspace(d, T, g_gru_grad_history.load(std::memory_order_relaxed) != 0);
 }
 
@@ -1656,6 +1662,9 @@ extern "C" int d2d_gru_grad(const d2d_gru_desc* d, int32_t T, const void* obs, c
     d2d_set_error("d2d_gru_grad: T=%d is not a whole number of %d-slot episodes", T, d->episode_length);
     return D2D_EINVAL;
   }
+  if (d->hidden > kGruNarrowHidden)  // 65..128: chunked BPTT + wgrad kernels of gru_wide_kernels.hip
+    return gru_wide_grad(d, T, obs, actions, logp_old, logp_strides, weight, weight_strides, clip, beta, scale, g_w_ih,
+                         g_w_hh, g_b_ih, g_b_hh, g_w1, g_b1, g_w2, g_b2, stats, workspace, workspace_floats, stream);
   const bool history = g_gru_grad_history.load(std::memory_order_relaxed) != 0;  // one snapshot per launch
   const int64_t need = gru_grad_workspace(d, T, history);
   if (workspace_floats < need) {

@@ -1,6 +1,6 @@
-"""Python entry to the GRU window-policy kernels (C ABI d2d_policy_gru / d2d_gru_grad,
-csrc/gru_kernels.hip): the reference's RNN module (algorithms/ippo.py:14-51 == d2d_ppo.py:24-59)
-for every agent at once, windows rebuilt in-kernel from the rollout buffer."""
+"""Python entry to the GRU window-policy kernels (C ABI d2d_policy_gru / d2d_gru_grad; csrc/gru_kernels.hip up
+to hidden 64, csrc/gru_wide_kernels.hip for 65..128): the reference's RNN module (algorithms/ippo.py:14-51 ==
+d2d_ppo.py:24-59) for every agent at once, windows rebuilt in-kernel from the rollout buffer."""
 import ctypes
 
 import torch
@@ -124,11 +124,14 @@ _ws = _Workspace()
 
 
 def grads(params, obs, kind, history_len, episode_length, weight, actions=None, logp_old=None, clip=0.1, beta=0.01,
-          scale=None, grads=None, stats=None):
+          scale=None, grads=None, stats=None, workspace=None):
     """Gradients of every agent's loss w.r.t. its RNN params (what autograd leaves in .grad):
     actors (kind 'sigmoid' / 'softmax'): -mean min(r W, clip(r) W) - beta mean entropy over the padded
     training windows of every sample; value (kind None): mean (V - R)^2, weight = R.
-    weight / logp_old: [T][E][N] or [N][E*T] (env-major), any strides.  Returns (grads, stats [N][2])."""
+    weight / logp_old: [T][E][N] or [N][E*T] (env-major), any strides.  Returns (grads, stats [N][2]).
+    workspace: an optional float32 device tensor to use as the kernels' scratch in place of the module's own buffer of
+    d2d_gru_grad_workspace floats.  Hidden sizes above 64 run the batch in chunks of as many 16-sample tiles per agent
+    as the scratch holds (any size from one tile of every agent on; less is refused), so its size sets the chunking."""
     lib = _lib.require_gpu()
     T, E, N, F = obs.shape
     k = KIND[kind]
@@ -140,12 +143,20 @@ def grads(params, obs, kind, history_len, episode_length, weight, actions=None, 
         stats = torch.empty((N, 2), dtype=torch.float32, device=dev)
     if scale is None:
         scale = 1.0 / (T * E) if T * E else 0.0    # an empty batch: every gradient and loss sum is zero
-    ws = _ws.get(lib.d2d_gru_grad_workspace(ctypes.byref(d), T), dev)
+    if workspace is None:
+        ws_floats = lib.d2d_gru_grad_workspace(ctypes.byref(d), T)  # (not the buffer's size: a larger one left by an
+        ws = _ws.get(ws_floats, dev)                                #  earlier call would change the chunking)
+        if d.hidden <= 64:
+            ws_floats = ws.numel()                                  # the narrow path gets what it always got
+    else:
+        if workspace.dtype != torch.float32 or workspace.device != dev or not workspace.is_contiguous():
+            raise ValueError("workspace must be a contiguous float32 tensor on the device of obs")
+        ws, ws_floats = workspace, workspace.numel()
     lo_st = _arr(_strides3(logp_old, T, E, N)) if logp_old is not None else None
     rc = lib.d2d_gru_grad(ctypes.byref(d), T, optr, None if actions is None else _ptr(actions),
                           None if logp_old is None else _ptr(logp_old), lo_st, _ptr(weight),
                           _arr(_strides3(weight, T, E, N)), float(clip), float(beta), float(scale),
                           *(_ptr(grads[n]) for n in ("w_ih", "w_hh", "b_ih", "b_hh", "w1", "b1", "w2", "b2")),
-                          _ptr(stats), ws.data_ptr(), ws.numel(), _lib.stream_ptr())
+                          _ptr(stats), _ptr(ws), int(ws_floats), _lib.stream_ptr())
     _lib.check(rc, "d2d_gru_grad")
     return grads, stats

@@ -455,7 +455,11 @@ int d2d_central_critic_dw1(int32_t hidden, int64_t B, int32_t S, int64_t ldx, co
  * S = min(p + 1, history_len) obs of the episode, unpadded (rollout / test, ippo.py:302-304, 362-364)
  * or front-zero-padded to history_len steps (training, preprocess_input_for_rnn ippo.py:390-403);
  * h0 = 0 for every window.  Sampling as d2d_policy_mlp_step (Philox stream 3, sample index
- * (s - slot0) * n_envs + e, i.e. the env index for one-slot launches). */
+ * (s - slot0) * n_envs + e, i.e. the env index for one-slot launches).
+ * Envelope: hidden in [1, 128], obs_dim + 1 <= 64, n_out <= 16 (else D2D_EUNSUPPORTED).  hidden <= 64 runs the kernels
+ * of gru_kernels.hip (weights as LDS images, vectors in registers); hidden in [65, 128] -- the learners' default 128
+ * and the RNN module's 100 -- runs gru_wide_kernels.hip (weights from L2, vectors in LDS, every product exact fp32)
+ * behind the same entry points, with history_len <= 256.  Both take fp32 rows or the compact record. */
 typedef struct d2d_gru_desc {
     int32_t n_agents, n_envs, obs_dim, hidden, n_out, kind;
     int32_t history_len, episode_length;
@@ -482,7 +486,8 @@ int d2d_policy_gru(const d2d_gru_desc* desc, int32_t T, const void* obs, int32_t
  * launch runs the window's last step only.  Every launch whose next window extends its own (p + 1 < history_len)
  * writes h after its window to hcarry.  carry_in requires p in [1, history_len - 1] (else D2D_EINVAL) and the
  * previous launch on hcarry to have been slot - 1 of the same buffer, batch and weights (the caller's sequence).
- * Actions, log-probs and values are bitwise those of d2d_policy_gru (the same steps on the same h). */
+ * Actions, log-probs and values are bitwise those of d2d_policy_gru (the same steps on the same h).
+ * d2d_gru_carry_floats: -1 for a desc outside the envelope.  hidden > 64: hcarry must be 16-byte aligned. */
 int64_t d2d_gru_carry_floats(const d2d_gru_desc* desc);
 int d2d_policy_gru_carry(const d2d_gru_desc* desc, int32_t T, const void* obs, int32_t slot, const void* forced,
                          uint32_t rng_step, int32_t deterministic, void* actions, float* out, float* hcarry,
@@ -492,7 +497,14 @@ int d2d_policy_gru_carry(const d2d_gru_desc* desc, int32_t T, const void* obs, i
  * the iPPO GRU critic's MSE (ippo.py:210-216) over every sample of the buffer (training windows, padded):
  * the gradients of all tensors above (overwritten) and stats [N][2] = (sum min-surrogate, sum entropy)
  * or (sum (V - R)^2, 0).  actions / logp_old / weight strides as d2d_ppo_actor_grad; weight = advantage
- * or M (kinds 0, 1), return target (kind 2).  obs_dim <= 31.  workspace: d2d_gru_grad_workspace floats. */
+ * or M (kinds 0, 1), return target (kind 2).  workspace: d2d_gru_grad_workspace floats.
+ * hidden > 64: the x, h and gate history of a PPO batch (16 L (5 * 16 ceil(H / 16) + 16 ceil(F / 16)) floats per agent
+ * and 16-sample tile) does not fit memory at once, so the batch runs in chunks of whole tiles, one BPTT + weight-
+ * gradient kernel pair per chunk, the later chunks adding to the outputs in stream order (fixed order, no atomics:
+ * two calls with the same workspace size give the same bits).  d2d_gru_grad_workspace answers min(the whole batch,
+ * 2^29 floats = 2 GiB -- 768 one-wave workgroups at 64 agents, L = 64, H = 128, three to a CU of 256), at least one
+ * tile of every agent; d2d_gru_grad takes any 16-byte aligned workspace from one tile of every agent on, sizes its
+ * chunks by it, and refuses a smaller one with D2D_EINVAL. */
 int64_t d2d_gru_grad_workspace(const d2d_gru_desc* desc, int32_t T);
 int d2d_gru_grad(const d2d_gru_desc* desc, int32_t T, const void* obs, const void* actions, const float* logp_old,
                  const int64_t* logp_strides, const float* weight, const int64_t* weight_strides, float clip,

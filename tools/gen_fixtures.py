@@ -504,7 +504,52 @@ DEFAULT_VARIANTS = {
 }
 
 
+# GRU traces above hidden 64, on the wide kernels (gen_learner_wide).  A trace stores four copies of every net (init,
+# final, two Adam steps' gradients) and a GRU net is 4 H^2 + 3 H F floats.  The project's limit for a committed file
+# is 1 MiB (1,048,576 B; the drivers' traces of 2.2-4.5 MB are older than it, gen_irdqn_fixtures.py asserts the same),
+# so agents are cut, not keys: one H = 128 actor alone is 1.07 MB with the chsel kind's 8 inputs, so the H = 128 trace
+# has one device on one channel (6 inputs), and the multi-agent and GRU-critic traces sit at H = 68 / 72 / 84.
+#   rnn_comb_h72:  D2D-PPO on devices 0 and 3 of the comb kind's setup (a periodic and an aperiodic one: the env
+#                  wants both kinds, so there is no one-device comb trace) -- the sigmoid head, the record input,
+#                  the carried rollout state; five hidden tiles, 8 of 16 units in the last;
+#   rnn_cat_h84:   iPPO, so the GRU critic is in it, on the first device of the chsel kind -- the softmax head on
+#                  fp32 rows; six tiles, 4 units in the last;
+#   rnn_cat3_h68:  D2D-PPO on the first three devices of the chsel kind, 4 episodes -- fp32 rows with the 1/n ACK
+#                  fractions of shared channels (15 of 80 rows per agent), three agents' softmax heads; five tiles,
+#                  4 units in the last;
+#   rnn_cat1_h128: D2D-PPO on the first device of the chsel kind with one channel -- the learners' default
+#                  hidden_size, all eight hidden tiles.
+WIDE_VARIANTS = {
+    "rnn_comb_h72": ("comb2", True, True, 4, 72, 20, ("d2d",), 2),
+    "rnn_cat_h84": ("chsel1", True, False, 3, 84, 20, ("ippo",), 2),
+    "rnn_cat3_h68": ("chsel3", True, False, 3, 68, 20, ("d2d",), 4),
+    "rnn_cat1_h128": ("chsel1c1", True, False, 3, 128, 20, ("d2d",), 2),
+}
+
+
 def _learner_env(kind, episode_length=20):
+    if kind in ("chsel3", "chsel1c1"):
+        mod = ref_module("envs.channel_selection_env")
+        n = 3 if kind == "chsel3" else 1
+        p = dict(n_agents=n, n_channels=3 if kind == "chsel3" else 1, deadlines=np.array([4, 6, 4][:n]),
+                 lbdas=np.array([0.6] * n), episode_length=episode_length, traffic_model="aperiodic",
+                 channel_switch=np.array([0.5, 0.3, 0.7, 0.2]))
+        return mod.ChannelSelectionEnv(**p), p
+    if kind == "comb2":
+        mod = ref_module("envs.combinatorial_env")
+        setup8 = safe_pickle.load(f"{DATA}/setup_8_channels.p")
+        dv = [0, 3]  # one periodic and one aperiodic device of the setup (the env wants both kinds)
+        p = dict(n_agents=2, n_channels=8, deadlines=setup8["deadlines"][dv], lbdas=np.array([0.5] * 2),
+                 period=np.array([2] * 2), arrival_probs=setup8["arrival_probs"][dv], offsets=setup8["offsets"][dv],
+                 episode_length=episode_length, traffic_model="heterogeneous", homogeneous_size=False,
+                 periodic_devices=[0], channel_switch=setup8["channel_switch"][dv])
+        return mod.CombinatorialEnv(**p), p
+    if kind == "chsel1":
+        mod = ref_module("envs.channel_selection_env")
+        p = dict(n_agents=1, n_channels=3, deadlines=np.array([4]), lbdas=np.array([0.6]),
+                 episode_length=episode_length, traffic_model="aperiodic",
+                 channel_switch=np.array([0.5, 0.3, 0.7, 0.2]))
+        return mod.ChannelSelectionEnv(**p), p
     if kind == "comb_xpload":
         # xp_load.py:60-75 on setup_8_channels at load 1/2, homogeneous obs (14 + 2 * 8 = 30 inputs)
         mod = ref_module("envs.combinatorial_env")
@@ -573,7 +618,8 @@ def gen_learner(only=None, episodes=2, suffix="", algos=("ippo", "d2d"), variant
         if only and vname not in only:
             continue
         for algo in (("ippo",) if kind == "single" else v_algos):
-            out = {"kind": "comb" if kind.startswith("comb") else kind, "useRNN": useRNN, "combinatorial": comb,
+            out = {"kind": "comb" if kind.startswith("comb") else "chsel" if kind.startswith("chsel") else kind,
+                   "useRNN": useRNN, "combinatorial": comb,
                    "history_len": hl, "hidden": hidden, "gamma": 0.6, "episode_length": ep_len, "episodes": episodes}
             env, params = _learner_env(kind, ep_len)
             out["params_json"] = json.dumps({k: _jsonable(v) for k, v in params.items()})
@@ -673,6 +719,15 @@ def gen_learner_defaults():
     gen_learner(only=[], variants=DEFAULT_VARIANTS)
 
 
+def gen_learner_wide():
+    """GRU traces at hidden sizes above 64 (WIDE_VARIANTS)."""
+    gen_learner(only=[], variants=WIDE_VARIANTS)
+    for vname, v in WIDE_VARIANTS.items():
+        for algo in v[6]:
+            path = os.path.join(OUT, f"learner_{algo}_{vname}.npz")
+            assert os.path.getsize(path) < (1 << 20), (path, os.path.getsize(path))
+
+
 def gen_learner_drivers():
     """GRU traces at the reference drivers' own network shapes (DRIVER_VARIANTS): hidden 64 with a
     16-step window, and the 6 x 16-channel env with 46 inputs."""
@@ -725,7 +780,8 @@ if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     table = {"data": gen_data, "env": gen_env, "d2denv": gen_d2denv, "gae": gen_gae, "learner": gen_learner,
              "baselines": gen_baselines, "evaltest": gen_evaltest, "learner4": gen_learner4,
-             "learner_drivers": gen_learner_drivers, "learner_defaults": gen_learner_defaults}
+             "learner_drivers": gen_learner_drivers, "learner_defaults": gen_learner_defaults,
+             "learner_wide": gen_learner_wide}
     # `learner <variant> ...` regenerates only the named learner variants
     which = sys.argv[1:2] if sys.argv[1:2] == ["learner"] else sys.argv[1:]
     for w in which or list(table):
