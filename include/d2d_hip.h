@@ -231,7 +231,9 @@ int d2d_buffer_words(int32_t max_deadline);
  *   R = r + gamma * R' * (1 - done_t),  delta = r + gamma V' (1-done_t) - V,
  *   gae = delta + gamma*lam*(1-done_t)*gae,  adv = gae + V  (quirk Q1),
  * except the globally last element (e = E-1, t = T-1 on the last shard),
- * whose adv is r - V (ippo.py:94).
+ * whose adv is r - V (ippo.py:94).  With dones[T-1] = 0 every env is still an
+ * independent sequence with zero bootstrap (R' = V' = gae = 0 at t = T-1): the
+ * env-major concatenation equivalence needs dones[T-1] = 1.
  *   rewards [T][E][reward_cols] (reward_cols 1 = broadcast over columns, or cols),
  *   values [T][E][cols], dones [T] (every env's sequence ends at t = T-1)
  *   adv, ret [T][E][cols] float (raw, un-normalised)                     */
