@@ -132,11 +132,14 @@ class BatchedLearnerBase(DataParallelMixin):
 
     # ------------------------------------------------ behaviour policy slot
     def _fused_ok(self):
-        """The fused HIP policy kernel covers the MLP policies (A <= 16, F <= 64; H <= 128 with F + 1 <= 32 --
-        the learners' default hidden_size 128 on the reference envs -- else H <= 64)."""
+        """The fused HIP policy kernels cover the MLP policies with A <= 16 and F <= 64: H <= 64 at any F, H <= 128
+        with F + 1 <= 32 (the learners' default hidden_size 128 on the reference envs; csrc/policy_kernels.hip),
+        and H in (64, 128] with F + 1 in (32, 64] -- the default hidden_size on the 16-channel envs -- on the wide
+        kernels (csrc/mlp_wide_kernels.hip; d2dhip._lib.mlp_wide is the rule, mlp_entry picks the C entry)."""
         if getattr(self, "_fused", None) is None:
+            from d2dhip._lib import mlp_wide
             p = self.policy
-            hmax = 128 if p.F + 1 <= 32 else 64
+            hmax = 128 if (p.F + 1 <= 32 or mlp_wide(p.F, p.H)) else 64
             self._fused = (not self.useRNN and p.kind == "mlp" and p.H <= hmax and p.A <= 16 and p.F <= 64
                            and os.environ.get("D2D_FUSED_POLICY", "1") != "0")
         return self._fused
@@ -164,7 +167,8 @@ class BatchedLearnerBase(DataParallelMixin):
 
     def _record_ok(self):
         # the combinatorial env's record, and since round 6 the D2DEnv's (categorical learners; record rows of at most
-        # 64 bytes -- the update kernels' F + 1 <= 64 -- and 64 agents, the ring / small neighbourhoods of the drivers)
+        # 64 bytes -- the update kernels' F + 1 <= 64 -- and 64 agents, the ring / small neighbourhoods of the drivers);
+        # the 64-byte record also at the default hidden_size 128 since the wide MLP kernels (_fused_ok)
         s = self.env.spec if self.kind == "single" else None
         env_ok = ((self.kind == "comb" and bool(self.combinatorial))
                   or (self.kind == "single" and not self.combinatorial and s.N <= 64 and _lib_record_bytes(s.F) <= 64))
@@ -173,7 +177,8 @@ class BatchedLearnerBase(DataParallelMixin):
 
     def _fused_update_ok(self):
         """The fused HIP update kernels cover the MLP actors with F + 1 <= 64 inputs (and the iPPO
-        per-agent MLP critics; csrc/update_kernels.hip) and the GRU policies / critics up to H = 128
+        per-agent MLP critics; csrc/update_kernels.hip, and csrc/mlp_wide_kernels.hip for H in (64, 128] with
+        F + 1 in (32, 64]: the shapes _fused_ok() takes) and the GRU policies / critics up to H = 128
         (csrc/gru_kernels.hip, csrc/gru_wide_kernels.hip: see _gru_ok)."""
         if getattr(self, "_fused_upd", None) is None:
             self._fused_upd = (((self._fused_ok() and self.policy.F + 1 <= 64) or self._gru_ok())
@@ -212,9 +217,9 @@ class BatchedLearnerBase(DataParallelMixin):
         logp = torch.empty((N, TE), dtype=torch.float32, device=self.device)
         optr = set_format(desc, ro.obs)
         # actions = NULL (ABI 15): forced mode stores only the log-probs (the actions are the input)
-        rc = lib.d2d_policy_mlp_step(desc, optr, ro.actions.data_ptr(), 0, 0, None, logp.data_ptr(), None,
-                                     _lib.stream_ptr())
-        _lib.check(rc, "d2d_policy_mlp_step (forced)")
+        step, name = _lib.mlp_entry(lib, "policy", self.policy.F, self.policy.H)
+        rc = step(desc, optr, ro.actions.data_ptr(), 0, 0, None, logp.data_ptr(), None, _lib.stream_ptr())
+        _lib.check(rc, name + " (forced)")
         return logp
 
     def _policy_seed(self):
@@ -289,10 +294,11 @@ class BatchedLearnerBase(DataParallelMixin):
             if forced is not None:
                 fz = self._env_actions(forced).contiguous()
             optr = set_format(desc, obs_buf[i])
-            rc = lib.d2d_policy_mlp_step(desc, optr, None if fz is None else fz.data_ptr(),
-                                         b.rng_step, 0 if train else 1, act_out.data_ptr(), logp_out.data_ptr(),
-                                         None if val_out is None else val_out.data_ptr(), _lib.stream_ptr())
-            _lib.check(rc, "d2d_policy_mlp_step")
+            step, name = _lib.mlp_entry(lib, "policy", self.policy.F, self.policy.H)
+            rc = step(desc, optr, None if fz is None else fz.data_ptr(),
+                      b.rng_step, 0 if train else 1, act_out.data_ptr(), logp_out.data_ptr(),
+                      None if val_out is None else val_out.data_ptr(), _lib.stream_ptr())
+            _lib.check(rc, name)
             if val_out is not None and desc.v1 is None:
                 raise RuntimeError("critic values requested without an MLP critic")
             return act_out

@@ -261,7 +261,7 @@ class D2DPPO(BatchedLearnerBase):
         else:
             _, sa = actor_grads({k: v.data for k, v in pp.items()}, ro.obs, ro.actions, ro.logp.permute(0, 2, 1),
                                 M.view(N, T, E).permute(1, 2, 0), kind, clip=cliprange, beta=beta,
-                                grads=self._grad_buffers(pp))
+                                grads=self._grad_buffers(pp), wide=True)
         self._phase("actor_grad")
         self._reduce_grads(self.policy.parameters())
         self._phase("allreduce")

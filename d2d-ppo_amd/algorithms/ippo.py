@@ -254,7 +254,7 @@ class iPPO(BatchedLearnerBase):
             # the rollout critic's values (same weights) -- then its Adam step, then GAE for the actor (the two
             # optimizers are independent, so the order of the two updates does not change either)
             _, sv = critic_grads({k: v.data for k, v in vp.items()}, ro.obs, ro.ret_tne.permute(0, 2, 1),
-                                 grads=self._grad_buffers(vp), values=ro.values.permute(0, 2, 1))
+                                 grads=self._grad_buffers(vp), values=ro.values.permute(0, 2, 1), wide=True)
             self._phase("critic_grad")
             self._reduce_grads(self.value.parameters())
             self._phase("allreduce")
@@ -271,7 +271,7 @@ class iPPO(BatchedLearnerBase):
         else:
             _, sa = actor_grads({k: v.data for k, v in pp.items()}, ro.obs, ro.actions, ro.logp.permute(0, 2, 1),
                                 ro.adv_tne.permute(0, 2, 1), kind, clip=cliprange, beta=beta,
-                                grads=self._grad_buffers(pp))
+                                grads=self._grad_buffers(pp), wide=True)
         self._phase("actor_grad")
         self._reduce_grads(self.policy.parameters())
         self._phase("allreduce")
@@ -285,7 +285,7 @@ class iPPO(BatchedLearnerBase):
                               ro.ret_tne.permute(0, 2, 1), grads=self._grad_buffers(vp))
         else:
             _, sv = critic_grads({k: v.data for k, v in vp.items()}, ro.obs, ro.ret_tne.permute(0, 2, 1),
-                                 grads=self._grad_buffers(vp))
+                                 grads=self._grad_buffers(vp), wide=True)
         if not critic_first:
             self._phase("critic_grad")
             self._reduce_grads(self.value.parameters())

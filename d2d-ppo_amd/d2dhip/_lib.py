@@ -170,6 +170,14 @@ _SIGS = {
                                             _p, _p, _p, _p, _p, _p, ctypes.c_int64, _p]),
     "d2d_ppo_critic_grad_values": (ctypes.c_int, [ctypes.POINTER(MlpDesc), ctypes.c_int32, _p, _p, _p, ctypes.c_float,
                                                    _p, _p, _p, _p, _p, _p, ctypes.c_int64, _p, _p, _p]),
+    "d2d_policy_mlp_wide_step": (ctypes.c_int, [ctypes.POINTER(MlpDesc), _p, _p, ctypes.c_uint32, ctypes.c_int32, _p,
+                                                 _p, _p, _p]),
+    "d2d_ppo_wide_workspace": (ctypes.c_int64, [ctypes.c_int32] * 6),
+    "d2d_ppo_actor_grad_wide": (ctypes.c_int, [ctypes.POINTER(MlpDesc), ctypes.c_int32, _p, _p, _p, _p, _p, _p,
+                                                ctypes.c_float, ctypes.c_float, ctypes.c_float, _p, _p, _p, _p, _p, _p,
+                                                ctypes.c_int64, _p]),
+    "d2d_ppo_critic_grad_wide": (ctypes.c_int, [ctypes.POINTER(MlpDesc), ctypes.c_int32, _p, _p, _p, ctypes.c_float,
+                                                 _p, _p, _p, _p, _p, _p, ctypes.c_int64, _p, _p, _p]),
     "d2d_central_critic_blocks": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int64]),
     "d2d_central_critic_image_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32]),
     "d2d_central_critic_fwd": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, _p, _p, _p,
@@ -255,6 +263,24 @@ def check(rc, what):
         if rc == -2:
             raise NotImplementedError(f"{what}: {msg}")
         raise D2DHipError(f"{what} failed ({rc}): {msg}")
+
+
+def mlp_wide(obs_dim, hidden):
+    """The one rule that sends an MLP shape to the wide entry points (csrc/mlp_wide_kernels.hip): hidden in
+    (64, 128] with two input chunks, obs_dim + 1 in (32, 64].  Every other shape stays with the narrow kernels."""
+    return 64 < int(hidden) <= 128 and 32 < int(obs_dim) + 1 <= 64
+
+
+def mlp_entry(lib, what, obs_dim, hidden, allow_wide=True):
+    """(function, name) of the C entry for `what` in {"policy", "workspace", "actor_grad", "critic_grad"} at this
+    shape: the wide sibling inside mlp_wide()'s envelope, else the narrow one (the critic: its _values form).
+    allow_wide=False: the narrow one whatever the shape (d2dhip.update's default, whose callers opt in)."""
+    wide = allow_wide and mlp_wide(obs_dim, hidden)
+    name = {"policy": ("d2d_policy_mlp_step", "d2d_policy_mlp_wide_step"),
+            "workspace": ("d2d_ppo_workspace", "d2d_ppo_wide_workspace"),
+            "actor_grad": ("d2d_ppo_actor_grad", "d2d_ppo_actor_grad_wide"),
+            "critic_grad": ("d2d_ppo_critic_grad_values", "d2d_ppo_critic_grad_wide")}[what][1 if wide else 0]
+    return getattr(lib, name), name
 
 
 def ptr(t):

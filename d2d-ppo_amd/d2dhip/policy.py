@@ -1,4 +1,5 @@
-"""Python entry to the fused behaviour-policy kernel (C ABI d2d_policy_mlp_step)."""
+"""Python entry to the fused behaviour-policy kernels (C ABI d2d_policy_mlp_step, or d2d_policy_mlp_wide_step for
+hidden sizes 65..128 with 33..64 inputs: _lib.mlp_entry picks by shape)."""
 import torch
 
 from . import _lib
@@ -41,10 +42,11 @@ def policy_mlp_step(actor, obs, kind, critic=None, forced=None, rng_step=0, dete
                         p(critic["w2"]) if critic else None, p(critic["b2"]) if critic else None, int(seed),
                         int(env_base), rng_offset)
     optr = set_format(desc, obs)
-    rc = lib.d2d_policy_mlp_step(desc, optr, None if forced is None else forced.contiguous().data_ptr(),
-                                 int(rng_step), 1 if deterministic else 0,
-                                 actions.data_ptr() if store_actions else None, logp.data_ptr(),
-                                 value.data_ptr() if value is not None and want_value else None,
-                                 _lib.stream_ptr())
-    _lib.check(rc, "d2d_policy_mlp_step")
+    step, name = _lib.mlp_entry(lib, "policy", F, H)
+    rc = step(desc, optr, None if forced is None else forced.contiguous().data_ptr(),
+              int(rng_step), 1 if deterministic else 0,
+              actions.data_ptr() if store_actions else None, logp.data_ptr(),
+              value.data_ptr() if value is not None and want_value else None,
+              _lib.stream_ptr())
+    _lib.check(rc, name)
     return (actions if store_actions else None), logp, (value if critic is not None and want_value else None)

@@ -1,4 +1,5 @@
-"""Python entry to the fused PPO-update kernels (C ABI d2d_ppo_actor_grad / d2d_ppo_critic_grad).
+"""Python entry to the fused PPO-update kernels (C ABI d2d_ppo_actor_grad / d2d_ppo_critic_grad; with wide=True also
+their _wide siblings for hidden sizes 65..128 with 33..64 inputs: _lib.mlp_entry then picks by shape).
 
 The kernels return the gradients torch autograd would leave in `.grad` for every agent's
 loss (ippo.py:194-217, d2d_ppo.py:198-216); the optimizer step stays in torch.
@@ -55,10 +56,13 @@ def _grads_like(net, grads):
 
 
 def actor_grads(net, obs, actions, logp_old, weight, kind, clip=0.1, beta=0.01, scale=None, grads=None,
-                stats=None, workspace=None):
+                stats=None, workspace=None, wide=False):
     """net: dict w1 [N][H][F], b1 [N][H], w2 [N][A][H], b2 [N][A] (fp32, contiguous).
     obs [T][E][N][F] fp32 or an ObsRecord of that shape; actions [T][E][N] masks (kind 'comb') or uint8 ids ('chsel');
     logp_old / weight: [T][E][N] or [N][E*T] (env-major), any strides.
+    wide=False keeps this call on d2d_ppo_actor_grad, whose envelope it has always had (hidden > 64 with more than 31
+    inputs raises NotImplementedError, as tests/test_update_gpu.py pins); wide=True -- what the learners pass -- lets
+    _lib.mlp_entry send hidden 65..128 with 33..64 inputs to d2d_ppo_actor_grad_wide.
     Returns (grads dict like net, stats [N][2] = (sum min-surrogate, sum entropy))."""
     lib = _lib.require_gpu()
     T, E, N, F = obs.shape
@@ -76,24 +80,25 @@ def actor_grads(net, obs, actions, logp_old, weight, kind, clip=0.1, beta=0.01, 
     if stats is None:
         stats = torch.empty((N, 2), dtype=torch.float32, device=dev)
     H, A = net["w1"].shape[1], net["w2"].shape[1]
-    need = lib.d2d_ppo_workspace(N, T, E, F, H, A)
+    need = _lib.mlp_entry(lib, "workspace", F, H, wide)[0](N, T, E, F, H, A)
     ws = (workspace or _ws).get(need, dev)
     desc = _desc(net, E, k)
     optr = set_format(desc, obs)
-    rc = lib.d2d_ppo_actor_grad(desc, T, optr, actions.data_ptr(), logp_old.data_ptr(),
-                                _arr(_strides3(logp_old, T, E, N)), weight.data_ptr(),
-                                _arr(_strides3(weight, T, E, N)), float(clip), float(beta), float(scale),
-                                grads["w1"].data_ptr(), grads["b1"].data_ptr(), grads["w2"].data_ptr(),
-                                grads["b2"].data_ptr(), stats.data_ptr(), ws.data_ptr(), ws.numel(),
-                                _lib.stream_ptr())
-    _lib.check(rc, "d2d_ppo_actor_grad")
+    grad, name = _lib.mlp_entry(lib, "actor_grad", F, H, wide)
+    rc = grad(desc, T, optr, actions.data_ptr(), logp_old.data_ptr(),
+              _arr(_strides3(logp_old, T, E, N)), weight.data_ptr(),
+              _arr(_strides3(weight, T, E, N)), float(clip), float(beta), float(scale),
+              grads["w1"].data_ptr(), grads["b1"].data_ptr(), grads["w2"].data_ptr(),
+              grads["b2"].data_ptr(), stats.data_ptr(), ws.data_ptr(), ws.numel(),
+              _lib.stream_ptr())
+    _lib.check(rc, name)
     return grads, stats
 
 
-def critic_grads(net, obs, returns, scale=None, grads=None, stats=None, workspace=None, values=None):
+def critic_grads(net, obs, returns, scale=None, grads=None, stats=None, workspace=None, values=None, wide=False):
     """net: dict w1 [N][H][F], b1 [N][H], w2 [N][1][H], b2 [N][1].  returns [T][E][N] or [N][E*T].
     values: None, or an fp32 tensor viewed as [T][E][N] (or [N][E*T]) that receives V(obs) of every sample
-    (d2d_ppo_critic_grad_values: iPPO's rollout values from the first epoch's critic pass).
+    (d2d_ppo_critic_grad_values: iPPO's rollout values from the first epoch's critic pass).  wide: as actor_grads.
     Returns (grads, stats [N][2] = (sum (V - R)^2, 0))."""
     lib = _lib.require_gpu()
     T, E, N, F = obs.shape
@@ -107,17 +112,18 @@ def critic_grads(net, obs, returns, scale=None, grads=None, stats=None, workspac
     if stats is None:
         stats = torch.empty((N, 2), dtype=torch.float32, device=dev)
     H = net["w1"].shape[1]
-    need = lib.d2d_ppo_workspace(N, T, E, F, H, 1)
+    need = _lib.mlp_entry(lib, "workspace", F, H, wide)[0](N, T, E, F, H, 1)
     ws = (workspace or _ws).get(need, dev)
     desc = _desc(net, E, 0, critic=True)
     optr = set_format(desc, obs)
     if values is not None:
         assert values.dtype == torch.float32 and values.device == dev
-    rc = lib.d2d_ppo_critic_grad_values(desc, T, optr, returns.data_ptr(), _arr(_strides3(returns, T, E, N)),
-                                        float(scale), grads["w1"].data_ptr(), grads["b1"].data_ptr(),
-                                        grads["w2"].data_ptr(), grads["b2"].data_ptr(), stats.data_ptr(),
-                                        ws.data_ptr(), ws.numel(),
-                                        None if values is None else values.data_ptr(),
-                                        None if values is None else _arr(_strides3(values, T, E, N)), _lib.stream_ptr())
-    _lib.check(rc, "d2d_ppo_critic_grad_values")
+    grad, name = _lib.mlp_entry(lib, "critic_grad", F, H, wide)
+    rc = grad(desc, T, optr, returns.data_ptr(), _arr(_strides3(returns, T, E, N)),
+              float(scale), grads["w1"].data_ptr(), grads["b1"].data_ptr(),
+              grads["w2"].data_ptr(), grads["b2"].data_ptr(), stats.data_ptr(),
+              ws.data_ptr(), ws.numel(),
+              None if values is None else values.data_ptr(),
+              None if values is None else _arr(_strides3(values, T, E, N)), _lib.stream_ptr())
+    _lib.check(rc, name)
     return grads, stats

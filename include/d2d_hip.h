@@ -350,7 +350,9 @@ int d2d_happo_chain(int32_t n_agents, int32_t T, int32_t E, const float* adv, co
  * Sampling uses Philox stream 3 at (env_base + env, agent, rng_step).
  * Shapes: obs_dim <= 64, n_out <= 16, hidden <= 64, or hidden <= 128 when obs_dim + 1 <= 32 (the
  * learners' default hidden_size 128 on the reference envs; one wave per SIMD there), else D2D_EUNSUPPORTED;
- * the update kernels below take the same hidden limits with obs_dim + 1 <= 64. */
+ * the update kernels below take the same hidden limits with obs_dim + 1 <= 64.  The remaining corner, hidden in
+ * (64, 128] with obs_dim + 1 in (32, 64], runs on the wide entry points (d2d_policy_mlp_wide_step and the
+ * d2d_ppo_*_wide functions below). */
 typedef struct d2d_mlp_desc {
     int32_t n_agents, n_envs, obs_dim, hidden, n_out, kind;
     const float *w1, *b1, *w2, *b2;
@@ -419,6 +421,37 @@ int d2d_ppo_critic_grad_values(const d2d_mlp_desc* desc, int32_t T, const void* 
                                const int64_t* return_strides, float scale, float* gw1, float* gb1, float* gw2,
                                float* gb2, float* stats, float* workspace, int64_t workspace_floats, float* values,
                                const int64_t* values_strides, void* stream);
+
+/* ---- Wide MLP learners (added on top of ABI v15: new entry points, nothing existing changes) ----
+ * The entry points above refuse hidden > 64 together with obs_dim + 1 > 32.  These four take exactly that
+ * envelope -- 64 < hidden <= 128 (any value), 32 < obs_dim + 1 <= 64 (obs_dim 32..63), n_out <= 16, both
+ * kinds, fp32 rows or the compact record (64-byte rows here) -- and refuse every other shape with
+ * D2D_EUNSUPPORTED: the learners' default hidden_size 128 on the 16-channel combinatorial envs (obs_dim 39 / 46),
+ * on 8 channels with a deadline >= 16, on D2DEnv rows of 32..63 columns.  Arguments, semantics, random stream,
+ * log-prob formulas and output layouts are those of the sibling named beside each; the arithmetic is fp32 MFMA
+ * with the weights in LDS (csrc/mlp_wide_kernels.hip).  Every argument check runs before any HIP call; no
+ * allocation, no host synchronisation (graph-capturable); n_envs = 0 or n_agents = 0 writes nothing.
+ *   d2d_policy_mlp_wide_step  = d2d_policy_mlp_step (sampled / deterministic / forced; actions = NULL in forced
+ *                               mode only; value = NULL or no critic: the critic is not run)
+ *   d2d_ppo_wide_workspace    = d2d_ppo_workspace: floats of scratch for the two calls below (0 when there is no
+ *                               sample; a pure function of its arguments)
+ *   d2d_ppo_actor_grad_wide   = d2d_ppo_actor_grad
+ *   d2d_ppo_critic_grad_wide  = d2d_ppo_critic_grad_values (values = NULL: not wanted)
+ * The update sums run in a fixed order with no atomics (a repeated launch gives the same bits); T = 0 or
+ * n_envs = 0 zeroes the outputs and needs no workspace (workspace may be NULL then). */
+int d2d_policy_mlp_wide_step(const d2d_mlp_desc* desc, const void* obs, const void* forced, uint32_t rng_step,
+                             int32_t deterministic, void* actions, float* logp, float* value, void* stream);
+int64_t d2d_ppo_wide_workspace(int32_t n_agents, int32_t T, int32_t n_envs, int32_t obs_dim, int32_t hidden,
+                               int32_t n_out);
+int d2d_ppo_actor_grad_wide(const d2d_mlp_desc* desc, int32_t T, const void* obs, const void* actions,
+                            const float* logp_old, const int64_t* logp_strides, const float* weight,
+                            const int64_t* weight_strides, float clip, float beta, float scale, float* gw1,
+                            float* gb1, float* gw2, float* gb2, float* stats, float* workspace,
+                            int64_t workspace_floats, void* stream);
+int d2d_ppo_critic_grad_wide(const d2d_mlp_desc* desc, int32_t T, const void* obs, const float* returns,
+                             const int64_t* return_strides, float scale, float* gw1, float* gb1, float* gw2,
+                             float* gb2, float* stats, float* workspace, int64_t workspace_floats, float* values,
+                             const int64_t* values_strides, void* stream);
 
 /* ---- D2D-PPO central critic, forward + the backward's per-sample glue (ABI 12) -------------------------------
  * The Value network over the whole state (d2d_ppo.py:62-98: linear1 [H][S], relu, linear2 [1][H]) for every sample

@@ -527,7 +527,42 @@ WIDE_VARIANTS = {
 }
 
 
+# MLP traces at hidden sizes above 64 with 33..64 network inputs, on the wide MLP kernels (gen_learner_mlpwide;
+# csrc/mlp_wide_kernels.hip).  An MLP net at H = 128 and 46 inputs is 8,080 (actor, 16 outputs) + 6,145 (critic)
+# floats and a trace stores four copies, so agents are cut, not keys (1 MiB per committed file):
+#   mlp_comb16_h128: iPPO on the first three devices of run_ippo_combinatorial.py's 16-channel env (one periodic, two
+#                    aperiodic; obs of 39 / 46 / 39 columns) at the learners' default hidden_size -- the Bernoulli head
+#                    with int16 masks, the 64-byte record, heterogeneous in_dims, per-agent critics, deferred values,
+#                    all eight hidden tiles;
+#   mlp_comb16_h100: D2D-PPO on the first four devices of that env with a ragged hidden size (seven tiles, 4 of 16
+#                    units in the last) -- the forced log-prob pass and the agent chain;
+#   mlp_cat15_h80:   iPPO on a ChannelSelectionEnv with 15 channels (16 ids) and deadlines 16 / 18 / 17 / 16 (obs of
+#                    32 / 34 / 33 / 32 columns), 4 episodes -- the Categorical head on fp32 rows; four agents over 15
+#                    channels share one often enough for 1/n ACK fractions: 36 of the 320 obs rows hold one
+#                    (gen_learner_mlpwide prints the count and asserts it is not zero).
+MLPWIDE_VARIANTS = {
+    "mlp_comb16_h128": ("comb16x3", False, True, 4, 128, 20, ("ippo",), 2),
+    "mlp_comb16_h100": ("comb16x4", False, True, 4, 100, 20, ("d2d",), 2),
+    "mlp_cat15_h80": ("chsel15", False, False, 3, 80, 20, ("ippo",), 4),
+}
+
+
 def _learner_env(kind, episode_length=20):
+    if kind in ("comb16x3", "comb16x4"):
+        # the first n devices of run_ippo_combinatorial.py:29-76's env at load 1
+        mod = ref_module("envs.combinatorial_env")
+        n = int(kind[-1])
+        p = dict(n_agents=n, n_channels=16, deadlines=np.array([7, 14, 7, 14][:n]), lbdas=np.array([1.0] * n),
+                 period=np.array([1.0] * n), arrival_probs=np.array([0.4, 0.8, 0.4, 0.8][:n]), offsets=np.zeros(n),
+                 episode_length=episode_length, traffic_model="heterogeneous", periodic_devices=[0],
+                 channel_switch=np.array([0.8] * 16))
+        return mod.CombinatorialEnv(**p), p
+    if kind == "chsel15":
+        mod = ref_module("envs.channel_selection_env")
+        p = dict(n_agents=4, n_channels=15, deadlines=np.array([16, 18, 17, 16]), lbdas=np.array([0.6] * 4),
+                 episode_length=episode_length, traffic_model="aperiodic",
+                 channel_switch=np.array([0.5, 0.3, 0.7, 0.2] * 4))
+        return mod.ChannelSelectionEnv(**p), p
     if kind in ("chsel3", "chsel1c1"):
         mod = ref_module("envs.channel_selection_env")
         n = 3 if kind == "chsel3" else 1
@@ -728,6 +763,25 @@ def gen_learner_wide():
             assert os.path.getsize(path) < (1 << 20), (path, os.path.getsize(path))
 
 
+def gen_learner_mlpwide():
+    """MLP traces at hidden sizes above 64 with 33..64 inputs (MLPWIDE_VARIANTS)."""
+    gen_learner(only=[], variants=MLPWIDE_VARIANTS)
+    for vname, v in MLPWIDE_VARIANTS.items():
+        for algo in v[6]:
+            path = os.path.join(OUT, f"learner_{algo}_{vname}.npz")
+            assert os.path.getsize(path) <= (1 << 20), (path, os.path.getsize(path))
+            with np.load(path) as z:
+                assert int(z["hidden"]) > 64
+                rows = frac = 0
+                for k in range(len([f for f in z.files if f.startswith("ro/obs")])):
+                    o = z[f"ro/obs{k}"]
+                    assert 32 <= o.shape[1] <= 63, (path, k, o.shape)
+                    rows += o.shape[0]
+                    frac += int((o != np.round(o)).any(1).sum())
+            print(f"learner_{algo}_{vname}: {os.path.getsize(path)} bytes; {frac} of {rows} obs rows hold a fraction")
+            assert (frac > 0) == (vname == "mlp_cat15_h80"), (path, frac)
+
+
 def gen_learner_drivers():
     """GRU traces at the reference drivers' own network shapes (DRIVER_VARIANTS): hidden 64 with a
     16-step window, and the 6 x 16-channel env with 46 inputs."""
@@ -781,7 +835,7 @@ if __name__ == "__main__":
     table = {"data": gen_data, "env": gen_env, "d2denv": gen_d2denv, "gae": gen_gae, "learner": gen_learner,
              "baselines": gen_baselines, "evaltest": gen_evaltest, "learner4": gen_learner4,
              "learner_drivers": gen_learner_drivers, "learner_defaults": gen_learner_defaults,
-             "learner_wide": gen_learner_wide}
+             "learner_wide": gen_learner_wide, "learner_mlpwide": gen_learner_mlpwide}
     # `learner <variant> ...` regenerates only the named learner variants
     which = sys.argv[1:2] if sys.argv[1:2] == ["learner"] else sys.argv[1:]
     for w in which or list(table):
