@@ -149,11 +149,14 @@ class BatchedLearnerBase(DataParallelMixin):
         hidden_size and the RNN module's 100 included -- A <= 16 and F + 1 <= 64 inputs (xp_load's 30 inputs and
         run_ippo_combinatorial.py's 6 x 16-channel env with 14 + 2 * 16 = 46): csrc/gru_kernels.hip up to H = 64
         (weights in LDS, vectors in registers), csrc/gru_wide_kernels.hip for 65..128 (weights from L2, vectors in
-        LDS; history_len <= 256).  The C ABI picks the file by the hidden size; nothing else here depends on it."""
+        LDS; history_len <= 256).  The C ABI picks the file by the hidden size; nothing else here depends on it.
+        The softmax head at H <= 64 takes up to 32 ids (xp_gamma.py's 16-channel ChannelSelectionEnv: 17).  The
+        rule itself is d2dhip.gru.supported."""
         if getattr(self, "_gru", None) is None:
+            from d2dhip.gru import supported
             p = self.policy
-            self._gru = (self.useRNN and p.kind == "rnn" and p.A <= 16 and p.F + 1 <= 64
-                         and (p.H <= 64 or (p.H <= 128 and self.history_len <= 256))
+            self._gru = (self.useRNN and p.kind == "rnn"
+                         and supported(p.F, p.H, p.A, self._gru_kind(), self.history_len)
                          and (self.kind == "comb") == bool(self.combinatorial)
                          and os.environ.get("D2D_FUSED_POLICY", "1") != "0")
         return self._gru
@@ -172,6 +175,10 @@ class BatchedLearnerBase(DataParallelMixin):
         s = self.env.spec if self.kind == "single" else None
         env_ok = ((self.kind == "comb" and bool(self.combinatorial))
                   or (self.kind == "single" and not self.combinatorial and s.N <= 64 and _lib_record_bytes(s.F) <= 64))
+        if self.useRNN and env_ok:  # (the record input stops at 16 outputs: d2dhip.gru.supported)
+            from d2dhip.gru import supported
+            p = self.policy
+            env_ok = supported(p.F, p.H, p.A, self._gru_kind(), self.history_len, record=True)
         return (self.obs_record and env_ok
                 and (self._gru_ok() or (not self.useRNN and self._fused_ok())) and self._fused_update_ok())
 

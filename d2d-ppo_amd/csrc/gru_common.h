@@ -528,17 +528,19 @@ __device__ __forceinline__ void load_bhn(f32x4 (&bhn)[HT], const GruW& w, int k,
     }
 }
 
-// Zero-padded head image of one agent: W1p [HW][HW], W2p [16][HW], b1p [HW], b2p [16] (HW = 16 HT):
-// no masks in the fragment loads, every address an immediate offset from a per-lane base.
-template <int HT>
+// Zero-padded head image of one agent: W1p [HW][HW], W2p [16 AT][HW], b1p [HW], b2p [16 AT] (HW = 16 HT):
+// no masks in the fragment loads, every address an immediate offset from a per-lane base.  AT = action
+// tiles of the head's outputs: 1 (up to 16 outputs) or 2 (the categorical head with 17..32 ids; rows /
+// entries 16..31 are the second tile, zero past A).
+template <int HT, int AT = 1>
 struct HeadImg {
-  static constexpr int HW = 16 * HT, W1 = 0, W2 = HW * HW, B1 = W2 + 16 * HW, B2 = B1 + HW, SIZE = B2 + 16;
+  static constexpr int HW = 16 * HT, W1 = 0, W2 = HW * HW, B1 = W2 + 16 * AT * HW, B2 = B1 + HW, SIZE = B2 + 16 * AT;
 };
 
 // idx-th element of agent k's head image (threads of a workgroup or a grid fill it cooperatively)
-template <int HT>
+template <int HT, int AT = 1>
 __device__ __forceinline__ float head_img_elem(const GruW& w, int k, int H, int A, int idx) {
-  using HI = HeadImg<HT>;
+  using HI = HeadImg<HT, AT>;
   constexpr int HW = HI::HW;
   if (idx < HI::W2) {
     const int r = idx / HW, c = idx - r * HW;
@@ -557,11 +559,11 @@ __device__ __forceinline__ float head_img_elem(const GruW& w, int k, int H, int 
 }
 
 // Head forward: pre1 = W1 h + b1 (accumulator layout, unit 16t + 4g + r), y = relu(pre1),
-// lg = W2 y + b2 (rows = output 4g + r, sample i), from the padded head image.
-template <int HT>
+// lg[at] = W2 y + b2 (rows = output 16 at + 4g + r, sample i), from the padded head image.
+template <int HT, int AT = 1>
 __device__ __forceinline__ void gru_head(const float* img, const float (&h)[HT][4], f32x4 (&pre1)[HT],
-                                         float (&y)[HT][4], f32x4& lg, int g, int i) {
-  using HI = HeadImg<HT>;
+                                         float (&y)[HT][4], f32x4 (&lg)[AT], int g, int i) {
+  using HI = HeadImg<HT, AT>;
   constexpr int HW = HI::HW;
 #pragma unroll
   for (int t = 0; t < HT; ++t) {
@@ -578,16 +580,19 @@ __device__ __forceinline__ void gru_head(const float* img, const float (&h)[HT][
 #pragma unroll
     for (int r = 0; r < 4; ++r) y[t][r] = relu(acc[r]);
   }
-  f32x4 acc;
 #pragma unroll
-  for (int r = 0; r < 4; ++r) acc[r] = img[HI::B2 + 4 * g + r];
+  for (int at = 0; at < AT; ++at) {
+    f32x4 acc;
 #pragma unroll
-  for (int q = 0; q < HT; ++q) {
-    const f32x4 wv = *reinterpret_cast<const f32x4*>(img + HI::W2 + i * HW + 16 * q + 4 * g);
+    for (int r = 0; r < 4; ++r) acc[r] = img[HI::B2 + 16 * at + 4 * g + r];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) acc = mfma4(wv[r], y[q][r], acc);
+    for (int q = 0; q < HT; ++q) {
+      const f32x4 wv = *reinterpret_cast<const f32x4*>(img + HI::W2 + (16 * at + i) * HW + 16 * q + 4 * g);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc = mfma4(wv[r], y[q][r], acc);
+    }
+    lg[at] = acc;
   }
-  lg = acc;
 }
 
 }  // namespace d2d

@@ -101,8 +101,12 @@ constexpr int kFlushSteps = 64;  // BPTT steps per weight-gradient MFMA accumula
 // SPLIT: the step on v_mfma_f32_16x16x32_bf16 over exact three-way splits (gru_preact_split; LDS:
 // the split images, 108 KB at H = 64, F < 32), else on v_mfma_f32_16x16x4_f32 (gru_preact).  Plus the
 // head image and the 16 KB padding table of padded windows: 147.5 KB at H = 64.
-template <int HT, int IT, int KIND, int MODE, bool SPLIT>
+// AT = 2 (the categorical head with 17..32 ids): a second 16-id accumulator tile of logits -- the head
+// image grows by 16 HW + 16 floats (151.7 KB at H = 64) -- and the two-tile epilogue
+// (policy_epilogue_cat2); instantiated with MODE = kModeRuntime only.
+template <int HT, int IT, int KIND, int MODE, bool SPLIT, int AT = 1>
 __global__ __launch_bounds__(512, 1) void gru_policy_kernel(GruArgs a) {
+  static_assert(AT == 1 || (AT == 2 && KIND == kGruCategorical), "two action tiles: the categorical head only");
   constexpr int HW = 16 * HT, IW = 16 * IT, R3 = 3 * HW;
   using SP = GruSplit<HT, IT>;
   constexpr int IMG_BYTES = SPLIT ? 16 * (SP::WIH + SP::WHH) : 4 * (R3 * IW + R3 * HW);
@@ -111,18 +115,19 @@ __global__ __launch_bounds__(512, 1) void gru_policy_kernel(GruArgs a) {
   float* whh_s = wih_s + R3 * IW;
   bf16x8* wih_b = reinterpret_cast<bf16x8*>(img_raw);
   bf16x8* whh_b = wih_b + SP::WIH;
-  __shared__ float head_s[HeadImg<HT>::SIZE];
+  __shared__ float head_s[HeadImg<HT, AT>::SIZE];
   const int k = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, i = lane & 15;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int H = a.H, F = a.F, N = a.N, E = a.E;
   if constexpr (SPLIT) load_gru_split_images<HT, IT>(wih_b, whh_b, a.w, k, H, F, tid, blockDim.x);
   else load_gru_images<HT, IT>(wih_s, whh_s, a.w, k, H, F, tid, blockDim.x);
-  for (int idx = tid; idx < HeadImg<HT>::SIZE; idx += blockDim.x)
-    head_s[idx] = head_img_elem<HT>(a.w, k, H, KIND == kGruValue ? 1 : a.A, idx);
+  for (int idx = tid; idx < HeadImg<HT, AT>::SIZE; idx += blockDim.x)
+    head_s[idx] = head_img_elem<HT, AT>(a.w, k, H, KIND == kGruValue ? 1 : a.A, idx);
   f32x4 bhn[HT];
   load_bhn<HT>(bhn, a.w, k, H, g);
-  const uint32_t rng = (MODE == kModeSample && a.ep.rng_off) ? a.ep.rng_step + *a.ep.rng_off : a.ep.rng_step;
+  const bool sampling = MODE == kModeRuntime ? !a.ep.forced && !a.ep.deterministic : MODE == kModeSample;
+  const uint32_t rng = (sampling && a.ep.rng_off) ? a.ep.rng_step + *a.ep.rng_off : a.ep.rng_step;
   const SwzOff<IW> oi(g, i);
   const SwzOff<HW> oh(g, i);
   const XSigns<IT> xsg(a.ov, k);
@@ -217,18 +222,24 @@ __global__ __launch_bounds__(512, 1) void gru_policy_kernel(GruArgs a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) hc[(4 * t + r) * 64] = h[t][r];
     }
-    f32x4 pre1[HT], lg;
+    f32x4 pre1[HT], lg[AT];
     float y[HT][4];
-    gru_head<HT>(head_s + opaque_zero(), h, pre1, y, lg, g, i);
+    gru_head<HT, AT>(head_s + opaque_zero(), h, pre1, y, lg, g, i);
     const int samp = sl * E + env;  // slot-major sample index of the launch
     if constexpr (KIND == kGruValue) {
-      if (ok && g == 0) a.value_out[(size_t)k * a.ep.E + samp] = lg[0];
+      if (ok && g == 0) a.value_out[(size_t)k * a.ep.E + samp] = lg[0][0];
     } else {
 #pragma unroll
-      for (int r = 0; r < 4; ++r) lg[r] *= kLog2e;
-      // HALF = false: every lane group holds 4 outputs of the same sample
-      policy_epilogue<KIND == kGruBernoulli ? 0 : 1, false, false, MODE, false, KIND == kGruBernoulli>(
-          a.ep, lg, 0.f, samp, ok, k, g, rng);
+      for (int at = 0; at < AT; ++at)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) lg[at][r] *= kLog2e;
+      if constexpr (AT == 2) {
+        policy_epilogue_cat2<MODE>(a.ep, lg, samp, ok, k, g, rng);
+      } else {
+        // HALF = false: every lane group holds 4 outputs of the same sample
+        policy_epilogue<KIND == kGruBernoulli ? 0 : 1, false, false, MODE, false, KIND == kGruBernoulli>(
+            a.ep, lg[0], 0.f, samp, ok, k, g, rng);
+      }
     }
   }
 }
@@ -319,10 +330,11 @@ struct GruWAcc {
 
 // Head gradients of one wave in global memory, [v][64 lanes] (coalesced): dW1 tiles
 // D[unit 16t + 4g + r][unit 16U + i], dW2 tiles D[output 4g + r][unit 16U + i], and per-sample-lane
-// partial sums of db1 (unit 16t + 4g + r) and db2 (output 4g + r).
-template <int HT>
+// partial sums of db1 (unit 16t + 4g + r) and db2 (output 4g + r).  AT = 2 action tiles: the dW2 tiles
+// of outputs 16 at + 4g + r at W2 + (at HT + U) 4 + r, their db2 at B2 + 4 at + r.
+template <int HT, int AT = 1>
 struct GruHeadAcc {
-  static constexpr int W1 = 0, W2 = HT * HT * 4, B1 = W2 + HT * 4, B2 = B1 + HT * 4, NV = B2 + 4;
+  static constexpr int W1 = 0, W2 = HT * HT * 4, B1 = W2 + AT * HT * 4, B2 = B1 + HT * 4, NV = B2 + 4 * AT;
 };
 
 // base[(v0 + v) * 64 + lane] += d[v] for a block of per-lane sums: every old value is loaded before
@@ -415,10 +427,16 @@ __device__ __forceinline__ bf16x8 whh_dh_frag(const bf16x8* whh_b, int T, int t,
 // extra all-padding pass after the last round runs j = L-2 .. 0 once with dh += ent[j] at each step.
 // Exact in real arithmetic; in fp32 only the summation order of the padding rows' contributions changes.
 // Saves the padding steps' share of the BPTT: ~16 % at L = 64 (ep_len 200), ~60 % at L = 256.
-template <int HT, int IT, int KIND, bool SPLIT, bool COOP = false, bool LONGW = false>
+//
+// AT = 2 (the categorical head with 17..32 ids; never COOP: no env writes a softmax record that wide): the
+// head's logits, their gradient and the dW2 / db2 sums are two 16-id tiles.  The second tile's dlg y^T
+// product is a second pass over the same 16 scratch rows (16 more rows do not fit the HT = 1 scratch),
+// and dy = W2^T dlg runs over both tiles (8 k-steps).
+template <int HT, int IT, int KIND, bool SPLIT, bool COOP = false, bool LONGW = false, int AT = 1>
 __global__ __launch_bounds__(256, 1) void gru_grad_kernel(GruArgs a) {
   constexpr int HW = 16 * HT, R3 = 3 * HW, RT = R3 + 4, SROWS = 2 * HW;
   constexpr bool PADC = COOP;
+  static_assert(AT == 1 || (AT == 2 && KIND == kGruCategorical && !COOP), "two action tiles: categorical, not COOP");
   static_assert(!COOP || (HT == 4 && SPLIT), "COOP: H in (32, 64], the split step");
   static_assert(COOP || !LONGW, "LONGW: the cooperative path");
   using SP = GruSplit<HT, IT>;
@@ -472,7 +490,7 @@ __global__ __launch_bounds__(256, 1) void gru_grad_kernel(GruArgs a) {
   load_bhn<HT>(bhn, a.w, k, H, g);
   GruSAcc<HT> acc;
   acc.each([](int, float& x) { x = 0.f; });
-  using HI = HeadImg<HT>;
+  using HI = HeadImg<HT, AT>;
   const float* himg = a.himg + (size_t)k * HI::SIZE;  // padded head image (gru_images_kernel)
   // the input image of gru_common.h (bias column F) written by gru_wih_image_kernel: A fragments
   // straight from L2 every step (registers are the update kernel's scarce resource)
@@ -506,8 +524,8 @@ __global__ __launch_bounds__(256, 1) void gru_grad_kernel(GruArgs a) {
     for (int j = 0; j < L; ++j)
 #pragma unroll
       for (int t = 0; t < HT; ++t) reinterpret_cast<f32x4*>(ent + ((size_t)j * 64 + lane) * 4 * HT)[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-  float* hacc = a.hacc + wave_id * (size_t)GruHeadAcc<HT>::NV * 64;
-  for (int v = 0; v < GruHeadAcc<HT>::NV; ++v) hacc[v * 64 + lane] = 0.f;
+  float* hacc = a.hacc + wave_id * (size_t)GruHeadAcc<HT, AT>::NV * 64;
+  for (int v = 0; v < GruHeadAcc<HT, AT>::NV; ++v) hacc[v * 64 + lane] = 0.f;
   using WA = GruWAcc<HT, IT>;
   float* ghist = a.ghist + wave_id * (size_t)L * 5 * HW * 16;
   // per-wave weight-gradient sums in global memory: the row-history GEMMs' (!COOP), or (COOP) the
@@ -666,36 +684,44 @@ __global__ __launch_bounds__(256, 1) void gru_grad_kernel(GruArgs a) {
 
     // ---- head forward + loss gradient w.r.t. the head outputs (COOP: the scratch is the wave's region)
     auto head_phase = [&]() {
-    f32x4 pre1[HT], lg;
+    f32x4 pre1[HT], lg[AT];
     float y[HT][4];
     const float* hi_ = himg + opaque_zero();
-    gru_head<HT>(hi_, h, pre1, y, lg, g, i);
-    f32x4 dlg;
+    gru_head<HT, AT>(hi_, h, pre1, y, lg, g, i);
+    f32x4 dlg[AT];
     if constexpr (KIND == kGruValue) {
-      const float d = lg[0] - in.w;  // V - R
+      const float d = lg[0][0] - in.w;  // V - R
       acc.st[0] += (ok && g == 0) ? d * d : 0.f;
-      dlg = f32x4{(ok && g == 0) ? 2.f * a.scale * d : 0.f, 0.f, 0.f, 0.f};
+      dlg[0] = f32x4{(ok && g == 0) ? 2.f * a.scale * d : 0.f, 0.f, 0.f, 0.f};
+    } else if constexpr (AT == 2) {
+      ppo_dz_cat2(a, lg, in.act, in.lo, in.w, ok, g, acc.st[0], acc.st[1], dlg);
     } else {
-      dlg = ppo_dz<KIND == kGruBernoulli ? 0 : 1, false, KIND == kGruBernoulli>(a, lg, in.act, in.lo, in.w, ok, g,
-                                                                                  acc.st[0], acc.st[1]);
+      dlg[0] = ppo_dz<KIND == kGruBernoulli ? 0 : 1, false, KIND == kGruBernoulli>(a, lg[0], in.act, in.lo, in.w, ok, g,
+                                                                                     acc.st[0], acc.st[1]);
     }
 
     // ---- head backward.  dW2 += dlg y^T, db2, dy = W2^T dlg, dpre1 = dy [pre1 > 0]; dW1 += dpre1 h_L^T,
     // db1; dh_L = W1^T dpre1.  The head's gradient sums are read-modified-written in the wave's global block.
     // (the per-tile sums are batched: a block's old values are all loaded before any is written back,
     // one memory wait per block instead of one per value)
-    using HA = GruHeadAcc<HT>;
-    static_assert(HA::B1 == HA::W2 + 4 * HT && HA::B2 == HA::B1 + 4 * HT, "head sums: W2 | b1 | b2 contiguous");
-    float hd[8 * HT + 4];  // this tile's dW2 (4U + r), db1 (4HT + 4t + r), db2 (8HT + r)
+    using HA = GruHeadAcc<HT, AT>;
+    static_assert(HA::B1 == HA::W2 + 4 * HT * AT && HA::B2 == HA::B1 + 4 * HT, "head sums: W2 | b1 | b2 contiguous");
+    // this tile's dW2 (4 (at HT + U) + r), db1 (4 HT AT + 4t + r), db2 (4 HT (AT + 1) + 4 at + r)
+    constexpr int HD1 = 4 * HT * AT, HD2 = HD1 + 4 * HT;
+    float hd[HD2 + 4 * AT];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      sc[(4 * g + r) * 16 + pcol(i)] = dlg[r];
-      hd[8 * HT + r] = dlg[r];
+    for (int at = 0; at < AT; ++at) {
+      if (at > 0) lds_order();  // the first tile's reads of rows 0..15 before the second tile overwrites them
 #pragma unroll
-      for (int t = 0; t < HT; ++t) sc[(16 + 16 * t + 4 * g + r) * 16 + pcol(i)] = y[t][r];
-    }
-    lds_order();
-    {
+      for (int r = 0; r < 4; ++r) {
+        sc[(4 * g + r) * 16 + pcol(i)] = dlg[at][r];
+        hd[HD2 + 4 * at + r] = dlg[at][r];
+        if (at == 0) {
+#pragma unroll
+          for (int t = 0; t < HT; ++t) sc[(16 + 16 * t + 4 * g + r) * 16 + pcol(i)] = y[t][r];
+        }
+      }
+      lds_order();
       const f32x4 af = sc_frag(sc, i, g);
 #pragma unroll
       for (int U = 0; U < HT; ++U) {
@@ -704,7 +730,7 @@ __global__ __launch_bounds__(256, 1) void gru_grad_kernel(GruArgs a) {
 #pragma unroll
         for (int s4 = 0; s4 < 4; ++s4) d = mfma4(af[s4], bf[s4], d);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) hd[4 * U + r] = d[r];
+        for (int r = 0; r < 4; ++r) hd[4 * (at * HT + U) + r] = d[r];
       }
     }
     float dpre1[HT][4];
@@ -712,11 +738,14 @@ __global__ __launch_bounds__(256, 1) void gru_grad_kernel(GruArgs a) {
     for (int t = 0; t < HT; ++t) {
       f32x4 dy = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int s4 = 0; s4 < 4; ++s4) dy = mfma4(hi_[HI::W2 + (4 * g + s4) * HW + 16 * t + i], dlg[s4], dy);
+      for (int at = 0; at < AT; ++at)
+#pragma unroll
+        for (int s4 = 0; s4 < 4; ++s4)
+          dy = mfma4(hi_[HI::W2 + (16 * at + 4 * g + s4) * HW + 16 * t + i], dlg[at][s4], dy);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         dpre1[t][r] = pre1[t][r] > 0.f ? dy[r] : 0.f;
-        hd[4 * HT + 4 * t + r] = dpre1[t][r];
+        hd[HD1 + 4 * t + r] = dpre1[t][r];
       }
     }
     rmw_block(hacc, lane, HA::W2, hd);
@@ -1244,7 +1273,7 @@ __global__ __launch_bounds__(256, 1) void gru_grad_kernel(GruArgs a) {
           }
         }
     // the head's sums: the workgroup's four wave blocks in fixed order
-    using HA = GruHeadAcc<HT>;
+    using HA = GruHeadAcc<HT, AT>;
     const float* hb = a.hacc + (size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 4 * HA::NV * 64;
     auto hsum = [&](int v) {
       return ((hb[v * 64 + lane] + hb[(HA::NV + v) * 64 + lane]) + hb[(2 * HA::NV + v) * 64 + lane]) +
@@ -1261,13 +1290,15 @@ __global__ __launch_bounds__(256, 1) void gru_grad_kernel(GruArgs a) {
           if (row < H && col < H) part[o.w1 + row * H + col] = v;
         }
 #pragma unroll
-    for (int U = 0; U < HT; ++U)
+    for (int at = 0; at < AT; ++at)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = 4 * g + r, col = 16 * U + i;
-        const float v = hsum(HA::W2 + 4 * U + r);
-        if (row < A && col < H) part[o.w2 + row * H + col] = v;
-      }
+      for (int U = 0; U < HT; ++U)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = 16 * at + 4 * g + r, col = 16 * U + i;
+          const float v = hsum(HA::W2 + 4 * (at * HT + U) + r);
+          if (row < A && col < H) part[o.w2 + row * H + col] = v;
+        }
     // bias sums: the 16 sample lanes of each row group
 #pragma unroll
     for (int t = 0; t < HT; ++t)
@@ -1281,10 +1312,12 @@ __global__ __launch_bounds__(256, 1) void gru_grad_kernel(GruArgs a) {
         }
       }
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float sb2 = row_sum16(hsum(HA::B2 + r));
-      if (i == 0 && 4 * g + r < A) part[o.b2 + 4 * g + r] = sb2;
-    }
+    for (int at = 0; at < AT; ++at)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float sb2 = row_sum16(hsum(HA::B2 + 4 * at + r));
+        if (i == 0 && 16 * at + 4 * g + r < A) part[o.b2 + 16 * at + 4 * g + r] = sb2;
+      }
     float s0 = acc.st[0], s1 = acc.st[1];
     s0 = group_sum(row_sum16(s0));
     s1 = group_sum(row_sum16(s1));
@@ -1297,13 +1330,13 @@ __global__ __launch_bounds__(256, 1) void gru_grad_kernel(GruArgs a) {
 
 // The input images of all agents, unswizzled: img[k][R][c] (gate row R of the padded layout, input
 // column c; column F = the biases of gru_common.h), zero outside the real rows / columns.
-template <int HT>
+template <int HT, int AT = 1>
 __global__ void gru_head_image_kernel(GruW w, int N, int H, int A, float* img) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  constexpr int SZ = HeadImg<HT>::SIZE;
+  constexpr int SZ = HeadImg<HT, AT>::SIZE;
   if (idx >= (int64_t)N * SZ) return;
   const int k = (int)(idx / SZ);
-  img[idx] = head_img_elem<HT>(w, k, H, A, (int)(idx - (int64_t)k * SZ));
+  img[idx] = head_img_elem<HT, AT>(w, k, H, A, (int)(idx - (int64_t)k * SZ));
 }
 
 // the fp32 input image that gru_grad_kernel's SPLIT = false body reads.  d2d_gru_grad launches only SPLIT = true
@@ -1365,6 +1398,18 @@ static void launch_policy_split(const GruArgs& a, dim3 grid, int threads, hipStr
 // when D2D_OPT_POLICY_F32_MFMA asks for it (A/B timing and tests)
 template <int HT, int IT, int KIND>
 static void launch_policy_mode(const GruArgs& a, dim3 grid, int threads, hipStream_t s) {
+  if constexpr (KIND == kGruCategorical) {
+    if (a.A > 16) {  // two action tiles; sample / deterministic / forced decided in the kernel (kModeRuntime)
+      if constexpr (IT <= 2) {
+        if (!g_policy_f32_mfma.load(std::memory_order_relaxed)) {
+          hipLaunchKernelGGL((gru_policy_kernel<HT, IT, KIND, kModeRuntime, true, 2>), grid, dim3(threads), 0, s, a);
+          return;
+        }
+      }
+      hipLaunchKernelGGL((gru_policy_kernel<HT, IT, KIND, kModeRuntime, false, 2>), grid, dim3(threads), 0, s, a);
+      return;
+    }
+  }
   if constexpr (IT <= 2) {
     if (!g_policy_f32_mfma.load(std::memory_order_relaxed)) {
       launch_policy_split<HT, IT, KIND, true>(a, grid, threads, s);
@@ -1397,7 +1442,23 @@ static int check_gru_desc(const d2d_gru_desc* d, const void* obs) {
   if (d->hidden < 1 || d->hidden > kGruWideHidden) { d2d_set_error("hidden=%d outside [1,%d]", d->hidden, kGruWideHidden); return D2D_EUNSUPPORTED; }
   if (d->obs_dim < 1 || d->obs_dim + 1 > 64) { d2d_set_error("obs_dim=%d outside [1,63]", d->obs_dim); return D2D_EUNSUPPORTED; }
   if (d->kind < 0 || d->kind > 2) { d2d_set_error("kind=%d outside [0,2]", d->kind); return D2D_EINVAL; }
-  if (d->kind != 2 && (d->n_out < 1 || d->n_out > 16)) { d2d_set_error("n_out=%d outside [1,16]", d->n_out); return D2D_EUNSUPPORTED; }
+  if (d->kind != 2 && (d->n_out < 1 || d->n_out > 32)) { d2d_set_error("n_out=%d outside [1,32]", d->n_out); return D2D_EUNSUPPORTED; }
+  if (d->kind != 2 && d->n_out > 16) {
+    // the second action tile: the categorical head of the hidden <= 64 kernels on fp32 rows
+    if (d->kind != 1) {
+      d2d_set_error("n_out=%d > 16 needs kind 1 (softmax): the sigmoid head takes up to 16 channels", d->n_out);
+      return D2D_EUNSUPPORTED;
+    }
+    if (d->hidden > kGruNarrowHidden) {
+      d2d_set_error("n_out=%d > 16 needs hidden <= %d (hidden=%d: the wide kernels take up to 16 outputs)", d->n_out,
+                    kGruNarrowHidden, d->hidden);
+      return D2D_EUNSUPPORTED;
+    }
+    if (d->obs_format == D2D_OBS_U8) {
+      d2d_set_error("n_out=%d > 16 needs fp32 obs rows: the compact record input takes up to 16 outputs", d->n_out);
+      return D2D_EUNSUPPORTED;
+    }
+  }
   if (d->history_len < 1 || d->episode_length < 1) { d2d_set_error("history_len / episode_length < 1"); return D2D_EINVAL; }
   const float* f32;
   const uint8_t* rec;
@@ -1547,7 +1608,8 @@ std::atomic<int> g_gru_grad_history{0};
 static bool gru_coop(int htp, int itp, bool u8, bool history) {
   return !history && htp == 4 && itp <= 3 && u8;
 }
-static GruWs gru_ws_layout(int64_t G, int64_t N, int64_t P, int64_t L, int htp, int itp, bool coop) {
+// atp: action tiles of the head (2: the categorical head with 17..32 ids)
+static GruWs gru_ws_layout(int64_t G, int64_t N, int64_t P, int64_t L, int htp, int itp, bool coop, int atp) {
   auto up = [](int64_t v) { return (v + 63) / 64 * 64; };
   const int64_t waves = G * N * 4, HW = 16 * htp;
   GruWs w;
@@ -1558,8 +1620,8 @@ static GruWs gru_ws_layout(int64_t G, int64_t N, int64_t P, int64_t L, int htp, 
   // fp32 input images [N][3 HW][16 itp] or the split ones [N][3 htp][CI][3 parts][64] 16-byte words
   const int64_t ci = (itp + 1) / 2;
   w.hacc = w.wimg + up(N * std::max<int64_t>(3 * HW * 16 * itp, 3 * htp * ci * 3 * 64 * 4));
-  w.himg = w.hacc + up(waves * 64 * (htp * htp * 4 + htp * 8 + 4));
-  w.ghist = w.himg + up(N * (HW * HW + 16 * HW + HW + 16));
+  w.himg = w.hacc + up(waves * 64 * (htp * htp * 4 + htp * 4 * atp + htp * 4 + 4 * atp));  // GruHeadAcc::NV
+  w.ghist = w.himg + up(N * (HW * HW + 16 * atp * HW + HW + 16 * atp));                    // HeadImg::SIZE
   w.gpart = w.ghist + (coop ? 0 : up(waves * L * 5 * HW * 16));  // COOP: no row history
   // wave sums: all dW tiles per wave (history), or (COOP) the wave's own 3 (HT + IT) tiles
   w.total = w.gpart + up(waves * 64 * (coop ? 3 * (htp + itp) * 4 : 3 * htp * (htp + itp) * 4));
@@ -1568,6 +1630,8 @@ static GruWs gru_ws_layout(int64_t G, int64_t N, int64_t P, int64_t L, int htp, 
 
 // 16-column input tiles of the x operand (the inputs and the bias column F): F + 1 <= 64
 static int gru_input_tiles(int F) { return F + 1 <= 16 ? 1 : F + 1 <= 32 ? 2 : F + 1 <= 48 ? 3 : 4; }
+// 16-output action tiles of the head
+static int gru_action_tiles(int A) { return A <= 16 ? 1 : 2; }
 
 static int64_t gru_grad_workspace(const d2d_gru_desc* d, int32_t T, bool history) {
   if (!d || d->n_agents <= 0 || T <= 0 || d->n_envs <= 0 || d->hidden < 1 || d->history_len < 1) return 0;
@@ -1576,7 +1640,8 @@ static int64_t gru_grad_workspace(const d2d_gru_desc* d, int32_t T, bool history
   const int G = gru_grad_blocks(d->n_agents, tiles);
   const GruOff o(H, d->obs_dim, A);
   return gru_ws_layout(G, d->n_agents, o.P, d->history_len, ht, gru_input_tiles(d->obs_dim),
-                       gru_coop(ht, gru_input_tiles(d->obs_dim), d->obs_format == D2D_OBS_U8, history)).total;
+                       gru_coop(ht, gru_input_tiles(d->obs_dim), d->obs_format == D2D_OBS_U8, history),
+                       gru_action_tiles(A)).total;
 }
 
 extern "C" int64_t d2d_gru_grad_workspace(const d2d_gru_desc* d, int32_t T) {
@@ -1587,6 +1652,10 @@ extern "C" int64_t d2d_gru_grad_workspace(const d2d_gru_desc* d, int32_t T) {
 
 template <int HT, int IT>
 static void launch_grad_kind(const GruArgs& a, dim3 grid, hipStream_t s, bool coop) {
+  if (a.kind == kGruCategorical && a.A > 16) {  // two action tiles (fp32 rows: never the cooperative path)
+    hipLaunchKernelGGL((gru_grad_kernel<HT, IT, kGruCategorical, true, false, false, 2>), grid, dim3(256), 0, s, a);
+    return;
+  }
   if constexpr (HT == 4 && IT <= 3) {
     if (coop && a.L > kFlushSteps) {
       if (a.kind == kGruBernoulli)
@@ -1686,7 +1755,8 @@ extern "C" int d2d_gru_grad(const d2d_gru_desc* d, int32_t T, const void* obs, c
   a.P = o.P;
   const int ht = (a.H + 15) / 16, htp = ht <= 1 ? 1 : ht <= 2 ? 2 : 4, itp = gru_input_tiles(a.F);
   const bool coop = gru_coop(htp, itp, a.ov.u8 != 0, history);
-  const GruWs ws = gru_ws_layout(a.G, a.N, a.P, a.L, htp, itp, coop);
+  const int atp = gru_action_tiles(a.A);
+  const GruWs ws = gru_ws_layout(a.G, a.N, a.P, a.L, htp, itp, coop, atp);
   a.partial = workspace + ws.partial;
   a.hist = workspace + ws.hist;
   a.wimg = workspace + ws.wimg;
@@ -1716,9 +1786,13 @@ extern "C" int d2d_gru_grad(const d2d_gru_desc* d, int32_t T, const void* obs, c
     if (htp == 1) launch_wih_split<1>(a, itp, s);
     else if (htp == 2) launch_wih_split<2>(a, itp, s);
     else launch_wih_split<4>(a, itp, s);
-    const int64_t nh = (int64_t)a.N * (16 * htp * 16 * htp + 16 * 16 * htp + 16 * htp + 16);
+    const int64_t nh = (int64_t)a.N * (16 * htp * 16 * htp + 16 * atp * 16 * htp + 16 * htp + 16 * atp);
     const dim3 gh((unsigned)((nh + 255) / 256));
-    if (htp == 1) hipLaunchKernelGGL(gru_head_image_kernel<1>, gh, dim3(256), 0, s, a.w, a.N, a.H, a.A, a.himg);
+    if (atp == 2) {
+      if (htp == 1) hipLaunchKernelGGL((gru_head_image_kernel<1, 2>), gh, dim3(256), 0, s, a.w, a.N, a.H, a.A, a.himg);
+      else if (htp == 2) hipLaunchKernelGGL((gru_head_image_kernel<2, 2>), gh, dim3(256), 0, s, a.w, a.N, a.H, a.A, a.himg);
+      else hipLaunchKernelGGL((gru_head_image_kernel<4, 2>), gh, dim3(256), 0, s, a.w, a.N, a.H, a.A, a.himg);
+    } else if (htp == 1) hipLaunchKernelGGL(gru_head_image_kernel<1>, gh, dim3(256), 0, s, a.w, a.N, a.H, a.A, a.himg);
     else if (htp == 2) hipLaunchKernelGGL(gru_head_image_kernel<2>, gh, dim3(256), 0, s, a.w, a.N, a.H, a.A, a.himg);
     else hipLaunchKernelGGL(gru_head_image_kernel<4>, gh, dim3(256), 0, s, a.w, a.N, a.H, a.A, a.himg);
   }

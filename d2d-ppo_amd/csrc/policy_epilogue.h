@@ -232,4 +232,107 @@ __device__ __forceinline__ void policy_epilogue(const MlpArgs& a, f32x4 lg, floa
   }
 }
 
+// The categorical epilogue over TWO accumulator tiles (the GRU head with 17..32 ids): lane (g, i) holds
+// the logits (times log2 e) of ids 16 t + 4g + r of env i in lg[t][r] (t < 2, r < 4), zero-padded past A.
+// Same distribution rules as policy_epilogue's KIND 1: softmax over the A ids, Categorical(probs)
+// renormalises by tot = sum p, sampling by the inverse CDF of ONE Philox uniform -- counter (env, agent,
+// step, stream 3 | 0), u = (x >> 8) 2^-24 tot, the chosen id = the first id (0..A-1, all of tile 0 before
+// tile 1) whose running sum exceeds u, clamped to A - 1 --, the first index of the maximum when
+// deterministic, the id byte when forced; log-prob = log clamp(p_a / tot, eps, 1 - eps).
+template <int MODE = kModeRuntime>
+__device__ __forceinline__ void policy_epilogue_cat2(const MlpArgs& a, const f32x4 (&lg)[2], int env, bool env_ok,
+                                                     int k, int g, uint32_t rng) {
+  const int N = a.N, A = a.A;
+  const bool forced = MODE == kModeRuntime ? a.forced != nullptr : MODE == kModeForced;
+  const bool deterministic = MODE == kModeRuntime ? a.deterministic != 0 : MODE == kModeDeterministic;
+  // ---- softmax over the A ids of env i: 8 registers x 4 lane groups
+  float mx = -INFINITY;
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (16 * t + 4 * g + r < A) mx = fmax_raw(mx, lg[t][r]);
+  mx = group_max(mx);
+  float p[2][4], sum = 0.f;
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      p[t][r] = (16 * t + 4 * g + r < A) ? __builtin_amdgcn_exp2f(lg[t][r] - mx) : 0.f;  // v_exp_f32, 1 ulp
+      sum += p[t][r];
+    }
+  sum = group_sum(sum);
+  const float inv = __builtin_amdgcn_rcpf(sum);  // 1 ulp
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) p[t][r] *= inv;
+
+  const size_t cell = (size_t)env * N + k;
+  const uint32_t genv = (uint32_t)(a.env_base + (uint64_t)(env_ok ? env : 0));
+  const float eps = 1.1920928955078125e-07f;
+  float psum[2], tsum[2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    psum[t] = p[t][0] + p[t][1] + p[t][2] + p[t][3];
+    tsum[t] = group_sum(psum[t]);
+  }
+  const float tot = tsum[0] + tsum[1];
+  int chosen = 0;
+  if (forced) {
+    chosen = env_ok ? reinterpret_cast<const unsigned char*>(a.forced)[cell] : 0;
+  } else if (deterministic) {
+    // first index of the maximum (torch.argmax): in a lane the ids ascend with (t, r)
+    float bv = -INFINITY;
+    int bi = A;
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (16 * t + 4 * g + r < A && p[t][r] > bv) { bv = p[t][r]; bi = 16 * t + 4 * g + r; }
+#pragma unroll
+    for (int m = 16; m <= 32; m <<= 1) {
+      const float ov = uf(m == 16 ? partner16(fu(bv), g) : partner32(fu(bv), g));
+      const int oi = (int)(m == 16 ? partner16((uint32_t)bi, g) : partner32((uint32_t)bi, g));
+      if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+    }
+    chosen = bi;
+  } else {
+    const u32x4 rr = philox(genv, (uint32_t)k, rng, (kStreamPolicy << 24), a.seed);
+    const float u = (float)(rr.x >> 8) * (1.f / 16777216.f) * tot;
+    int pick_id = A;  // A = "not in my lane"
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      // exclusive sum of the tile's lane groups < g, after the whole of the tiles before it
+      const float s16 = uf(partner16(fu(psum[t]), g));  // partner in pair (g ^ 1)
+      const float s32 = uf(partner32(fu(psum[t] + s16), g));
+      float c = t == 0 ? 0.f : tsum[0];
+      if (g & 2) c += s32;
+      if (g & 1) c += s16;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        if (16 * t + 4 * g + r < A && pick_id == A) {
+          c += p[t][r];
+          if (u < c) pick_id = 16 * t + 4 * g + r;
+        }
+      }
+    }
+    const int best = group_min(pick_id);
+    chosen = best < A ? best : A - 1;  // rounding at the very top of the CDF
+  }
+  float lpv = 0.f;
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (16 * t + 4 * g + r == chosen)
+        lpv = hw_log2(fminf(fmaxf(p[t][r] * __builtin_amdgcn_rcpf(tot), eps), 1.f - eps)) * kLn2;
+  lpv = group_sum(lpv);
+  if (env_ok && g == 0) {
+    // forced mode with act_out NULL: the actions are the caller's input, nothing to store
+    if (!forced || a.act_out) reinterpret_cast<unsigned char*>(a.act_out)[cell] = (unsigned char)chosen;
+    a.logp_out[(size_t)k * a.E + env] = lpv;
+  }
+}
+
 }  // namespace d2d

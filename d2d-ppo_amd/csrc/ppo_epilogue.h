@@ -149,4 +149,92 @@ __device__ __forceinline__ f32x4 ppo_dz(const Args& a, f32x4 z, uint32_t act, fl
   }
 }
 
+// ppo_dz's Categorical case over TWO accumulator tiles (the GRU head with 17..32 ids): lane (g, i) holds
+// the logits of ids 16 t + 4g + r of sample i in z[t][r].  The same formulas, clamp and tie rules; every
+// per-sample sum runs over the lane's 8 values, then over the 4 lane groups.
+template <class Args>
+__device__ __forceinline__ void ppo_dz_cat2(const Args& a, const f32x4 (&z)[2], uint32_t act, float lo, float W,
+                                            bool ok, int g, float& surr_acc, float& ent_acc, f32x4 (&dz)[2]) {
+  const int A = a.A, aid = (int)act;
+  bool valid[2][4];
+  float mx = -INFINITY;
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      valid[t][r] = 16 * t + 4 * g + r < A;
+      if (valid[t][r]) mx = fmax_raw(mx, z[t][r]);
+    }
+  mx = group_max(mx);
+  float p[2][4], sum = 0.f;
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      p[t][r] = valid[t][r] ? __expf(z[t][r] - mx) : 0.f;
+      sum += p[t][r];
+    }
+  sum = group_sum(sum);
+  const float inv = __builtin_amdgcn_rcpf(sum);
+  float psum = 0.f;
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      p[t][r] *= inv;
+      psum += p[t][r];
+    }
+  psum = group_sum(psum);
+  const float ipsum = __builtin_amdgcn_rcpf(psum);
+  float q[2][4], gr[2][4], dsur[2][4], lsel = 0.f, esum = 0.f;
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      q[t][r] = p[t][r] * ipsum;
+      const float qc = fminf(fmaxf(q[t][r], kEps), 1.f - kEps);
+      const bool inside = qc == q[t][r];  // the clamp passes q through
+      const float lq = hw_log2(qc) * kLn2;
+      const bool chosen = valid[t][r] && 16 * t + 4 * g + r == aid;
+      lsel += chosen ? lq : 0.f;
+      esum += valid[t][r] ? q[t][r] * lq : 0.f;
+      const float iqc = __builtin_amdgcn_rcpf(qc);
+      dsur[t][r] = (chosen && inside) ? iqc : 0.f;
+      // d(-beta * ent)/dq = beta * (log qc + q * [inside] / qc)
+      gr[t][r] = valid[t][r] ? (lq + (inside ? q[t][r] * iqc : 0.f)) : 0.f;
+    }
+  const float logp = group_sum(lsel);
+  const float ent = -group_sum(esum);
+  const float ratio = __expf(logp - lo);
+  const float cr = __builtin_amdgcn_fmed3f(ratio, a.clip_lo, a.clip_hi);  // clamp: one v_med3_f32
+  const float s1 = ratio * W, s2 = cr * W;
+  const bool gate = (ratio >= a.clip_lo && ratio <= a.clip_hi) || s1 < s2;
+  const float coef = gate ? -a.scale * ratio * W : 0.f;
+  const float eb = a.beta * a.scale;
+  float gq = 0.f;
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      gr[t][r] = coef * dsur[t][r] + eb * gr[t][r];  // dL/dq
+      gq += gr[t][r] * q[t][r];
+    }
+  gq = group_sum(gq);
+  float dp[2][4], dot = 0.f;
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      dp[t][r] = valid[t][r] ? (gr[t][r] - gq) * ipsum : 0.f;  // through q = p / sum p
+      dot += p[t][r] * dp[t][r];
+    }
+  dot = group_sum(dot);
+  surr_acc += (ok && g == 0) ? fminf(s1, s2) : 0.f;
+  ent_acc += (ok && g == 0) ? ent : 0.f;
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) dz[t][r] = (ok && valid[t][r]) ? p[t][r] * (dp[t][r] - dot) : 0.f;
+}
+
 }  // namespace d2d

@@ -11,6 +11,21 @@ from .record import set_format
 KIND = {"sigmoid": 0, "softmax": 1, None: 2}
 
 
+def supported(F, H, A, kind, history_len, record=False):
+    """The envelope of the GRU kernels (check_gru_desc in csrc/gru_kernels.hip and the wide file's own checks), in
+    one place for the learners: F + 1 <= 64 inputs; hidden <= 64, or 65..128 with history_len <= 256; up to 16
+    outputs -- or 17..32 for the softmax head (kind 'softmax' / 1) at hidden <= 64 on fp32 obs rows (not the
+    compact record).  kind: 'sigmoid' / 'softmax' / None or the C codes 0 / 1 / 2 (value: A is ignored)."""
+    k = KIND.get(kind, kind)
+    if not (1 <= F and F + 1 <= 64 and 1 <= H and history_len >= 1):
+        return False
+    if not (H <= 64 or (H <= 128 and history_len <= 256)):
+        return False
+    if k == 2 or 1 <= A <= 16:
+        return True
+    return 17 <= A <= 32 and k == 1 and H <= 64 and not record
+
+
 _dummy = {}
 
 

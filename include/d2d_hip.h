@@ -491,7 +491,9 @@ int d2d_central_critic_dw1(int32_t hidden, int64_t B, int32_t S, int64_t ldx, co
  * or front-zero-padded to history_len steps (training, preprocess_input_for_rnn ippo.py:390-403);
  * h0 = 0 for every window.  Sampling as d2d_policy_mlp_step (Philox stream 3, sample index
  * (s - slot0) * n_envs + e, i.e. the env index for one-slot launches).
- * Envelope: hidden in [1, 128], obs_dim + 1 <= 64, n_out <= 16 (else D2D_EUNSUPPORTED).  hidden <= 64 runs the kernels
+ * Envelope: hidden in [1, 128], obs_dim + 1 <= 64, n_out <= 16 -- or n_out in [17, 32] for kind 1 (softmax) with
+ * hidden <= 64 on fp32 rows (a second 16-id tile of logits; not kind 0, not hidden > 64, not the compact record) --
+ * else D2D_EUNSUPPORTED.  hidden <= 64 runs the kernels
  * of gru_kernels.hip (weights as LDS images, vectors in registers); hidden in [65, 128] -- the learners' default 128
  * and the RNN module's 100 -- runs gru_wide_kernels.hip (weights from L2, vectors in LDS, every product exact fp32)
  * behind the same entry points, with history_len <= 256.  Both take fp32 rows or the compact record. */

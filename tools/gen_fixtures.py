@@ -547,7 +547,29 @@ MLPWIDE_VARIANTS = {
 }
 
 
+# GRU traces of the categorical head with 17 ids, on the second action tile of csrc/gru_kernels.hip
+# (gen_learner_actions): the first devices of xp_gamma.py:33-54's env -- 16 channels, deadlines 7, lbdas 1 / 3.5,
+# channel_switch 0.8 x 17, periodic device 2 where it is among them -- whose obs are 7 + 16 + 1 = 24 columns.  A trace
+# stores four copies of every net and must stay under the 1 MiB of a committed file: agents are cut, not keys.
+#   rnn_cat16_h64: D2D-PPO on the first two devices at the driver's own hidden_size 64 and history_len 10;
+#   rnn_cat16_h32: iPPO (the GRU critic is in it) on the first three devices, 4 episodes: three agents over 16
+#                  channels share one often enough for 1/n ACK fractions (the generator prints the count of obs rows
+#                  that hold one and asserts it is not zero).
+ACTIONS_VARIANTS = {
+    "rnn_cat16_h64": ("chsel16x2", True, False, 10, 64, 20, ("d2d",), 2),
+    "rnn_cat16_h32": ("chsel16x3", True, False, 3, 32, 20, ("ippo",), 4),
+}
+
+
 def _learner_env(kind, episode_length=20):
+    if kind in ("chsel16x2", "chsel16x3"):
+        mod = ref_module("envs.channel_selection_env")
+        n = int(kind[-1])
+        p = dict(n_agents=n, n_channels=16, deadlines=np.array([7] * n), period=np.array([7] * n),
+                 lbdas=np.array([1 / 3.5] * n), episode_length=episode_length, traffic_model="aperiodic",
+                 arrival_probs=np.array([1] * n), periodic_devices=np.array([2] if n > 2 else [], dtype=np.int64),
+                 offsets=np.array([0, 2, 4, 0, 2][:n]), channel_switch=np.array([0.8] * 17), verbose=False)
+        return mod.ChannelSelectionEnv(**p), p
     if kind in ("comb16x3", "comb16x4"):
         # the first n devices of run_ippo_combinatorial.py:29-76's env at load 1
         mod = ref_module("envs.combinatorial_env")
@@ -782,6 +804,26 @@ def gen_learner_mlpwide():
             assert (frac > 0) == (vname == "mlp_cat15_h80"), (path, frac)
 
 
+def gen_learner_actions():
+    """GRU traces of the categorical head with 17 ids (ACTIONS_VARIANTS)."""
+    gen_learner(only=[], variants=ACTIONS_VARIANTS)
+    for vname, v in ACTIONS_VARIANTS.items():
+        for algo in v[6]:
+            path = os.path.join(OUT, f"learner_{algo}_{vname}.npz")
+            assert os.path.getsize(path) <= (1 << 20), (path, os.path.getsize(path))
+            with np.load(path) as z:
+                rows = frac = 0
+                for k in range(len([f for f in z.files if f.startswith("ro/obs")])):
+                    o = z[f"ro/obs{k}"]
+                    assert o.shape[1] == 24, (path, k, o.shape)
+                    rows += o.shape[0]
+                    frac += int((o != np.round(o)).any(1).sum())
+                assert z["ro/actions"].max() >= 16, "no action id in the second tile"
+            print(f"learner_{algo}_{vname}: {os.path.getsize(path)} bytes; {frac} of {rows} obs rows hold a fraction")
+            if vname == "rnn_cat16_h32":
+                assert frac > 0, (path, frac)
+
+
 def gen_learner_drivers():
     """GRU traces at the reference drivers' own network shapes (DRIVER_VARIANTS): hidden 64 with a
     16-step window, and the 6 x 16-channel env with 46 inputs."""
@@ -835,7 +877,8 @@ if __name__ == "__main__":
     table = {"data": gen_data, "env": gen_env, "d2denv": gen_d2denv, "gae": gen_gae, "learner": gen_learner,
              "baselines": gen_baselines, "evaltest": gen_evaltest, "learner4": gen_learner4,
              "learner_drivers": gen_learner_drivers, "learner_defaults": gen_learner_defaults,
-             "learner_wide": gen_learner_wide, "learner_mlpwide": gen_learner_mlpwide}
+             "learner_wide": gen_learner_wide, "learner_mlpwide": gen_learner_mlpwide,
+             "learner_actions": gen_learner_actions}
     # `learner <variant> ...` regenerates only the named learner variants
     which = sys.argv[1:2] if sys.argv[1:2] == ["learner"] else sys.argv[1:]
     for w in which or list(table):
