@@ -135,12 +135,16 @@ class BatchedLearnerBase(DataParallelMixin):
         """The fused HIP policy kernels cover the MLP policies with A <= 16 and F <= 64: H <= 64 at any F, H <= 128
         with F + 1 <= 32 (the learners' default hidden_size 128 on the reference envs; csrc/policy_kernels.hip),
         and H in (64, 128] with F + 1 in (32, 64] -- the default hidden_size on the 16-channel envs -- on the wide
-        kernels (csrc/mlp_wide_kernels.hip; d2dhip._lib.mlp_wide is the rule, mlp_entry picks the C entry)."""
+        kernels (csrc/mlp_wide_kernels.hip; d2dhip._lib.mlp_wide is the rule, mlp_entry picks the C entry).  The
+        categorical head with 17..32 ids (a ChannelSelectionEnv with 16..31 channels: xp_gamma.py's 17 ids) runs at
+        any H <= 128 with F + 1 <= 64 on csrc/mlp_actions_kernels.hip (d2dhip._lib.mlp_actions is the rule)."""
         if getattr(self, "_fused", None) is None:
-            from d2dhip._lib import mlp_wide
+            from d2dhip._lib import mlp_actions, mlp_wide
             p = self.policy
             hmax = 128 if (p.F + 1 <= 32 or mlp_wide(p.F, p.H)) else 64
-            self._fused = (not self.useRNN and p.kind == "mlp" and p.H <= hmax and p.A <= 16 and p.F <= 64
+            shape_ok = ((p.H <= hmax and p.A <= 16 and p.F <= 64)
+                        or mlp_actions(p.F, p.H, p.A, 0 if self.combinatorial else 1))
+            self._fused = (not self.useRNN and p.kind == "mlp" and shape_ok
                            and os.environ.get("D2D_FUSED_POLICY", "1") != "0")
         return self._fused
 
@@ -185,7 +189,8 @@ class BatchedLearnerBase(DataParallelMixin):
     def _fused_update_ok(self):
         """The fused HIP update kernels cover the MLP actors with F + 1 <= 64 inputs (and the iPPO
         per-agent MLP critics; csrc/update_kernels.hip, and csrc/mlp_wide_kernels.hip for H in (64, 128] with
-        F + 1 in (32, 64]: the shapes _fused_ok() takes) and the GRU policies / critics up to H = 128
+        F + 1 in (32, 64], csrc/mlp_actions_kernels.hip for the categorical actor with 17..32 ids: the shapes
+        _fused_ok() takes) and the GRU policies / critics up to H = 128
         (csrc/gru_kernels.hip, csrc/gru_wide_kernels.hip: see _gru_ok)."""
         if getattr(self, "_fused_upd", None) is None:
             self._fused_upd = (((self._fused_ok() and self.policy.F + 1 <= 64) or self._gru_ok())
@@ -224,7 +229,7 @@ class BatchedLearnerBase(DataParallelMixin):
         logp = torch.empty((N, TE), dtype=torch.float32, device=self.device)
         optr = set_format(desc, ro.obs)
         # actions = NULL (ABI 15): forced mode stores only the log-probs (the actions are the input)
-        step, name = _lib.mlp_entry(lib, "policy", self.policy.F, self.policy.H)
+        step, name = _lib.mlp_entry(lib, "policy", self.policy.F, self.policy.H, n_out=self.policy.A, kind=desc.kind)
         rc = step(desc, optr, ro.actions.data_ptr(), 0, 0, None, logp.data_ptr(), None, _lib.stream_ptr())
         _lib.check(rc, name + " (forced)")
         return logp
@@ -301,7 +306,8 @@ class BatchedLearnerBase(DataParallelMixin):
             if forced is not None:
                 fz = self._env_actions(forced).contiguous()
             optr = set_format(desc, obs_buf[i])
-            step, name = _lib.mlp_entry(lib, "policy", self.policy.F, self.policy.H)
+            step, name = _lib.mlp_entry(lib, "policy", self.policy.F, self.policy.H, n_out=self.policy.A,
+                                        kind=desc.kind)
             rc = step(desc, optr, None if fz is None else fz.data_ptr(),
                       b.rng_step, 0 if train else 1, act_out.data_ptr(), logp_out.data_ptr(),
                       None if val_out is None else val_out.data_ptr(), _lib.stream_ptr())

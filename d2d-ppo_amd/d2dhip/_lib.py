@@ -178,6 +178,12 @@ _SIGS = {
                                                 ctypes.c_int64, _p]),
     "d2d_ppo_critic_grad_wide": (ctypes.c_int, [ctypes.POINTER(MlpDesc), ctypes.c_int32, _p, _p, _p, ctypes.c_float,
                                                  _p, _p, _p, _p, _p, _p, ctypes.c_int64, _p, _p, _p]),
+    "d2d_policy_mlp_actions_step": (ctypes.c_int, [ctypes.POINTER(MlpDesc), _p, _p, ctypes.c_uint32, ctypes.c_int32,
+                                                    _p, _p, _p, _p]),
+    "d2d_ppo_actions_workspace": (ctypes.c_int64, [ctypes.c_int32] * 6),
+    "d2d_ppo_actor_grad_actions": (ctypes.c_int, [ctypes.POINTER(MlpDesc), ctypes.c_int32, _p, _p, _p, _p, _p, _p,
+                                                   ctypes.c_float, ctypes.c_float, ctypes.c_float, _p, _p, _p, _p, _p,
+                                                   _p, ctypes.c_int64, _p]),
     "d2d_central_critic_blocks": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int64]),
     "d2d_central_critic_image_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32]),
     "d2d_central_critic_fwd": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, _p, _p, _p,
@@ -271,10 +277,22 @@ def mlp_wide(obs_dim, hidden):
     return 64 < int(hidden) <= 128 and 32 < int(obs_dim) + 1 <= 64
 
 
-def mlp_entry(lib, what, obs_dim, hidden, allow_wide=True):
+def mlp_actions(obs_dim, hidden, n_out, kind):
+    """The one rule that sends an MLP actor to the two-tile entry points (csrc/mlp_actions_kernels.hip): the
+    categorical head (kind 1 / "chsel") with 17..32 ids, hidden in [1, 128], obs_dim + 1 <= 64, fp32 rows."""
+    return (kind in (1, "chsel") and 17 <= int(n_out) <= 32 and 1 <= int(hidden) <= 128
+            and 1 <= int(obs_dim) and int(obs_dim) + 1 <= 64)
+
+
+def mlp_entry(lib, what, obs_dim, hidden, allow_wide=True, n_out=None, kind=None):
     """(function, name) of the C entry for `what` in {"policy", "workspace", "actor_grad", "critic_grad"} at this
-    shape: the wide sibling inside mlp_wide()'s envelope, else the narrow one (the critic: its _values form).
-    allow_wide=False: the narrow one whatever the shape (d2dhip.update's default, whose callers opt in)."""
+    shape: the actor's two-tile sibling inside mlp_actions()'s envelope (n_out and kind given; the critic does not
+    depend on them), else the wide sibling inside mlp_wide()'s envelope, else the narrow one (the critic: its _values
+    form).  allow_wide=False: never the wide one (d2dhip.update's default, whose callers opt in)."""
+    if what != "critic_grad" and n_out is not None and mlp_actions(obs_dim, hidden, n_out, kind):
+        name = {"policy": "d2d_policy_mlp_actions_step", "workspace": "d2d_ppo_actions_workspace",
+                "actor_grad": "d2d_ppo_actor_grad_actions"}[what]
+        return getattr(lib, name), name
     wide = allow_wide and mlp_wide(obs_dim, hidden)
     name = {"policy": ("d2d_policy_mlp_step", "d2d_policy_mlp_wide_step"),
             "workspace": ("d2d_ppo_workspace", "d2d_ppo_wide_workspace"),

@@ -1,5 +1,6 @@
 """Python entry to the fused behaviour-policy kernels (C ABI d2d_policy_mlp_step, or d2d_policy_mlp_wide_step for
-hidden sizes 65..128 with 33..64 inputs: _lib.mlp_entry picks by shape)."""
+hidden sizes 65..128 with 33..64 inputs, or d2d_policy_mlp_actions_step for the categorical head with 17..32 ids:
+_lib.mlp_entry picks by shape)."""
 import torch
 
 from . import _lib
@@ -42,7 +43,7 @@ def policy_mlp_step(actor, obs, kind, critic=None, forced=None, rng_step=0, dete
                         p(critic["w2"]) if critic else None, p(critic["b2"]) if critic else None, int(seed),
                         int(env_base), rng_offset)
     optr = set_format(desc, obs)
-    step, name = _lib.mlp_entry(lib, "policy", F, H)
+    step, name = _lib.mlp_entry(lib, "policy", F, H, n_out=A, kind=k)
     rc = step(desc, optr, None if forced is None else forced.contiguous().data_ptr(),
               int(rng_step), 1 if deterministic else 0,
               actions.data_ptr() if store_actions else None, logp.data_ptr(),

@@ -1,5 +1,6 @@
 """Python entry to the fused PPO-update kernels (C ABI d2d_ppo_actor_grad / d2d_ppo_critic_grad; with wide=True also
-their _wide siblings for hidden sizes 65..128 with 33..64 inputs: _lib.mlp_entry then picks by shape).
+their _wide siblings for hidden sizes 65..128 with 33..64 inputs: _lib.mlp_entry then picks by shape; a categorical
+actor with 17..32 ids goes to d2d_ppo_actor_grad_actions, which no older entry point takes, either way).
 
 The kernels return the gradients torch autograd would leave in `.grad` for every agent's
 loss (ippo.py:194-217, d2d_ppo.py:198-216); the optimizer step stays in torch.
@@ -62,7 +63,8 @@ def actor_grads(net, obs, actions, logp_old, weight, kind, clip=0.1, beta=0.01, 
     logp_old / weight: [T][E][N] or [N][E*T] (env-major), any strides.
     wide=False keeps this call on d2d_ppo_actor_grad, whose envelope it has always had (hidden > 64 with more than 31
     inputs raises NotImplementedError, as tests/test_update_gpu.py pins); wide=True -- what the learners pass -- lets
-    _lib.mlp_entry send hidden 65..128 with 33..64 inputs to d2d_ppo_actor_grad_wide.
+    _lib.mlp_entry send hidden 65..128 with 33..64 inputs to d2d_ppo_actor_grad_wide.  kind 'chsel' with 17..32 ids
+    (uint8 ids, fp32 rows) runs on d2d_ppo_actor_grad_actions whatever `wide` says (_lib.mlp_actions is the rule).
     Returns (grads dict like net, stats [N][2] = (sum min-surrogate, sum entropy))."""
     lib = _lib.require_gpu()
     T, E, N, F = obs.shape
@@ -80,11 +82,11 @@ def actor_grads(net, obs, actions, logp_old, weight, kind, clip=0.1, beta=0.01, 
     if stats is None:
         stats = torch.empty((N, 2), dtype=torch.float32, device=dev)
     H, A = net["w1"].shape[1], net["w2"].shape[1]
-    need = _lib.mlp_entry(lib, "workspace", F, H, wide)[0](N, T, E, F, H, A)
+    need = _lib.mlp_entry(lib, "workspace", F, H, wide, A, k)[0](N, T, E, F, H, A)
     ws = (workspace or _ws).get(need, dev)
     desc = _desc(net, E, k)
     optr = set_format(desc, obs)
-    grad, name = _lib.mlp_entry(lib, "actor_grad", F, H, wide)
+    grad, name = _lib.mlp_entry(lib, "actor_grad", F, H, wide, A, k)
     rc = grad(desc, T, optr, actions.data_ptr(), logp_old.data_ptr(),
               _arr(_strides3(logp_old, T, E, N)), weight.data_ptr(),
               _arr(_strides3(weight, T, E, N)), float(clip), float(beta), float(scale),

@@ -352,7 +352,8 @@ int d2d_happo_chain(int32_t n_agents, int32_t T, int32_t E, const float* adv, co
  * learners' default hidden_size 128 on the reference envs; one wave per SIMD there), else D2D_EUNSUPPORTED;
  * the update kernels below take the same hidden limits with obs_dim + 1 <= 64.  The remaining corner, hidden in
  * (64, 128] with obs_dim + 1 in (32, 64], runs on the wide entry points (d2d_policy_mlp_wide_step and the
- * d2d_ppo_*_wide functions below). */
+ * d2d_ppo_*_wide functions below); the categorical head with 17 <= n_out <= 32 on d2d_policy_mlp_actions_step and
+ * d2d_ppo_actor_grad_actions, further below. */
 typedef struct d2d_mlp_desc {
     int32_t n_agents, n_envs, obs_dim, hidden, n_out, kind;
     const float *w1, *b1, *w2, *b2;
@@ -452,6 +453,36 @@ int d2d_ppo_critic_grad_wide(const d2d_mlp_desc* desc, int32_t T, const void* ob
                              const int64_t* return_strides, float scale, float* gw1, float* gb1, float* gw2,
                              float* gb2, float* stats, float* workspace, int64_t workspace_floats, float* values,
                              const int64_t* values_strides, void* stream);
+
+/* ---- MLP learners with 17..32 action ids (added on top of ABI v15: new entry points, nothing existing changes) ----
+ * Every entry point above refuses n_out > 16.  These three take the categorical head (kind 1) with
+ * 17 <= n_out <= 32, 1 <= hidden <= 128 and obs_dim + 1 <= 64 on fp32 rows -- the MLP learners of a
+ * ChannelSelectionEnv with 16..31 channels (xp_gamma.py: 16 channels, 17 ids, 24 inputs) -- and refuse every other
+ * shape, kind 0 and the compact record (no env writes one for a head this wide) with D2D_EUNSUPPORTED and a message
+ * that states this envelope.  They replace, for these shapes, what their narrow siblings replace: Policy.forward +
+ * PPO.select_action (algorithms/ippo.py:54-90, 154-176; d2d_ppo.py:62-98, 159-181) and evaluate() + the actor loss +
+ * backward() of PPO.train_step (ippo.py:178-208; d2d_ppo.py:183-216).  Arguments, semantics, random stream (ONE
+ * Philox uniform per (env, agent, step), inverse CDF over ids 0..A-1), log-prob formulas, the 2^-23 clamp and output
+ * layouts are those of the sibling named beside each; actions are uint8 ids.  The arithmetic is fp32 MFMA with the
+ * weights in LDS (csrc/mlp_actions_kernels.hip).  Every argument check runs before any HIP call; no allocation, no
+ * host synchronisation (graph-capturable); n_envs = 0 or n_agents = 0 writes nothing.
+ *   d2d_policy_mlp_actions_step  = d2d_policy_mlp_step (sampled / deterministic / forced; actions = NULL in forced
+ *                                  mode only; value = NULL or no critic: the critic is not run)
+ *   d2d_ppo_actions_workspace    = d2d_ppo_workspace: 4 G N P floats, P = H F + H + A H + A + 2 and G the workgroups
+ *                                  per agent (0 when there is no sample; a pure function of its arguments)
+ *   d2d_ppo_actor_grad_actions   = d2d_ppo_actor_grad
+ * The per-agent critic does not depend on n_out: its update stays on d2d_ppo_critic_grad_values /
+ * d2d_ppo_critic_grad_wide.  The update sums run in a fixed order with no atomics (a repeated launch gives the same
+ * bits); T = 0 or n_envs = 0 zeroes the outputs and needs no workspace (workspace may be NULL then). */
+int d2d_policy_mlp_actions_step(const d2d_mlp_desc* desc, const void* obs, const void* forced, uint32_t rng_step,
+                                int32_t deterministic, void* actions, float* logp, float* value, void* stream);
+int64_t d2d_ppo_actions_workspace(int32_t n_agents, int32_t T, int32_t n_envs, int32_t obs_dim, int32_t hidden,
+                                  int32_t n_out);
+int d2d_ppo_actor_grad_actions(const d2d_mlp_desc* desc, int32_t T, const void* obs, const void* actions,
+                               const float* logp_old, const int64_t* logp_strides, const float* weight,
+                               const int64_t* weight_strides, float clip, float beta, float scale, float* gw1,
+                               float* gb1, float* gw2, float* gb2, float* stats, float* workspace,
+                               int64_t workspace_floats, void* stream);
 
 /* ---- D2D-PPO central critic, forward + the backward's per-sample glue (ABI 12) -------------------------------
  * The Value network over the whole state (d2d_ppo.py:62-98: linear1 [H][S], relu, linear2 [1][H]) for every sample

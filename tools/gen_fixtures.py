@@ -561,6 +561,22 @@ ACTIONS_VARIANTS = {
 }
 
 
+# MLP traces of the categorical head with 17 ids, on csrc/mlp_actions_kernels.hip (gen_learner_mlpactions): the first
+# devices of xp_gamma.py:33-54's env, as above (24 obs columns).  Agents are cut, not keys (1 MiB per committed file):
+#   mlp_cat16_h64:  iPPO (per-agent critics, deferred values) on the first three devices, 4 episodes: three agents over
+#                   16 channels share one often enough for 1/n ACK fractions (the generator asserts that some obs rows
+#                   hold one);
+#   mlp_cat16_h128: D2D-PPO on the first two devices at the learners' default hidden_size -- the forced log-prob pass
+#                   and the agent chain.
+# (the torch seed of the recorded rollout's action draws: 11 as everywhere, but for the iPPO trace, whose first seed with a
+# shared good channel -- a 1/n ACK -- in its 240 obs rows is the one below)
+MLPACTIONS_ROLLOUT_SEED = {"mlp_cat16_h64": 12}
+MLPACTIONS_VARIANTS = {
+    "mlp_cat16_h64": ("chsel16x3", False, False, 3, 64, 20, ("ippo",), 4),
+    "mlp_cat16_h128": ("chsel16x2", False, False, 3, 128, 20, ("d2d",), 2),
+}
+
+
 def _learner_env(kind, episode_length=20):
     if kind in ("chsel16x2", "chsel16x3"):
         mod = ref_module("envs.channel_selection_env")
@@ -662,7 +678,7 @@ def _tap_grads(out, tag, opt, net):
     opt.step = rec
 
 
-def gen_learner(only=None, episodes=2, suffix="", algos=("ippo", "d2d"), variants=None):
+def gen_learner(only=None, episodes=2, suffix="", algos=("ippo", "d2d"), variants=None, rollout_seed=11):
     import torch
     ippo = ref_module("algorithms.ippo")
     d2d = ref_module("algorithms.d2d_ppo")
@@ -697,7 +713,7 @@ def gen_learner(only=None, episodes=2, suffix="", algos=("ippo", "d2d"), variant
             # --- teacher-forced rollout: record actions + env draws of a real create_rollouts
             rec_env = RecordingEnv(env)
             lr.env = rec_env
-            torch.manual_seed(11)
+            torch.manual_seed(rollout_seed)
             ro = lr.create_rollouts(episodes)
             lr.env = env
             for k, v in rec_env.rec.items():
@@ -824,6 +840,28 @@ def gen_learner_actions():
                 assert frac > 0, (path, frac)
 
 
+def gen_learner_mlpactions():
+    """MLP traces of the categorical head with 17 ids (MLPACTIONS_VARIANTS)."""
+    for vname, v in MLPACTIONS_VARIANTS.items():
+        gen_learner(only=[], variants={vname: v}, rollout_seed=MLPACTIONS_ROLLOUT_SEED.get(vname, 11))
+    for vname, v in MLPACTIONS_VARIANTS.items():
+        for algo in v[6]:
+            path = os.path.join(OUT, f"learner_{algo}_{vname}.npz")
+            assert os.path.getsize(path) <= (1 << 20), (path, os.path.getsize(path))
+            with np.load(path) as z:
+                assert not bool(z["useRNN"])
+                rows = frac = 0
+                for k in range(len([f for f in z.files if f.startswith("ro/obs")])):
+                    o = z[f"ro/obs{k}"]
+                    assert o.shape[1] == 24, (path, k, o.shape)
+                    rows += o.shape[0]
+                    frac += int((o != np.round(o)).any(1).sum())
+                assert z["ro/actions"].max() >= 16, "no action id in the second tile"
+            print(f"learner_{algo}_{vname}: {os.path.getsize(path)} bytes; {frac} of {rows} obs rows hold a fraction")
+            if vname == "mlp_cat16_h64":
+                assert frac > 0, (path, frac)
+
+
 def gen_learner_drivers():
     """GRU traces at the reference drivers' own network shapes (DRIVER_VARIANTS): hidden 64 with a
     16-step window, and the 6 x 16-channel env with 46 inputs."""
@@ -878,7 +916,7 @@ if __name__ == "__main__":
              "baselines": gen_baselines, "evaltest": gen_evaltest, "learner4": gen_learner4,
              "learner_drivers": gen_learner_drivers, "learner_defaults": gen_learner_defaults,
              "learner_wide": gen_learner_wide, "learner_mlpwide": gen_learner_mlpwide,
-             "learner_actions": gen_learner_actions}
+             "learner_actions": gen_learner_actions, "learner_mlpactions": gen_learner_mlpactions}
     # `learner <variant> ...` regenerates only the named learner variants
     which = sys.argv[1:2] if sys.argv[1:2] == ["learner"] else sys.argv[1:]
     for w in which or list(table):
