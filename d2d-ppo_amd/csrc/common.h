@@ -124,9 +124,9 @@ __device__ __forceinline__ uint32_t pick(const u32x4& r, int i) {
 // t[x] = ceil(F_x * 2^32) - 1 (d2d_env_desc.poisson_cdf, built on the host in the same IEEE double
 // order): u >= F_x <=> r > t[x], t is nondecreasing and t[255] = 2^32 - 1, so the result is the
 // count of leading entries below r -- bitwise the division loop, at four compares per 16-byte load
-// instead of a double division per step.
-__device__ __forceinline__ uint32_t poisson_lookup(uint32_t r, const uint32_t* __restrict__ t) {
-  uint32_t x = 0;
+// instead of a double division per step.  x: the entries already counted (all below r, a multiple of 4), for a
+// caller that compared the head of the row from a copy of its own.
+__device__ __forceinline__ uint32_t poisson_lookup(uint32_t r, const uint32_t* __restrict__ t, uint32_t x = 0) {
   for (;;) {
     const uint4 q = *reinterpret_cast<const uint4*>(t + x);
     const uint32_t n = (uint32_t)(r > q.x) + (uint32_t)(r > q.y) + (uint32_t)(r > q.z) + (uint32_t)(r > q.w);

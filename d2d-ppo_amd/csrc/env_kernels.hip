@@ -40,6 +40,30 @@ constexpr int kCombWavesPerEu = 7;
 constexpr int kCombRecBlock = 256;
 constexpr int kMaxAgents = 1024;
 
+// The record-only wave step (comb_record_only): kRecOnly, the outputs it does not write and the replay inputs
+// it does not read are null at compile time; kRecTables, it also reads the per-agent tables from an LDS image
+// that the workgroup stages once, where the plain wave step has every wave fetch them through the vector
+// memory path (7 of its 10 loads) and wait for them in series behind the state.
+// At 64 x 8 x 65,536 (packed, CT = 8; alternating runs on one MI355X, profiles/env_tables/summary.json): step
+// 59.7 us on the plain wave step, 58.2 us record-only, 55.6 us with the tables at 7 waves per SIMD, 55.0 us at
+// 8 waves, 55.2 us at 8 waves in 512-lane blocks (eight envs per image; not separable from 256, which stays).
+// The kRecTables headline kernel at 8 waves: 64 VGPRs, 78 SGPRs, 11 SGPRs spilled to VGPR lanes (all of them in
+// the loop over records longer than 32 bytes: no v_writelane / v_readlane on the 32-byte record's path), no
+// scratch, 3,584 B of LDS.  The other instantiations keep kCombWavesPerEu.
+enum { kRecOff = 0, kRecOnly = 1, kRecTables = 2 };
+constexpr int kCombRecMode = kRecTables;
+constexpr int kCombTabWavesPerEu = 8;
+constexpr int kCombTabBlock = 256;
+// The image, in 32-bit words; lane k reads element k of each array, 16-byte elements at stride 16 B
+// (ds_read_b128 without bank conflicts) and words at stride 4 B.  The thresholds are narrowed to 32 bits:
+// "r < t" of a 32-bit draw r and t in [0, 2^32] is "r < min(t, 2^32 - 1) or t >= 2^32", exactly.
+constexpr int kTabMisc = 0;      // uint32[64]: deadline | obs_width << 8 | arrival_kind << 16
+constexpr int kTabAlways = 64;   // uint32[64]: bit c set where flip_thr[k][c] >= 2^32
+constexpr int kTabArr = 128;     // uint4[64]: a Poisson agent's pois_cdf[k][0..3]; any other agent's
+                                 // {min(arrival_thr, 2^32 - 1), arrival_thr >= 2^32, 0, 0}
+constexpr int kTabThr = 384;     // uint4[64] per four channels: min(flip_thr[k][c], 2^32 - 1), 0 for c >= C
+constexpr size_t comb_table_words(int C) { return (size_t)kTabThr + 4 * kWave * (size_t)((C + 3) / 4); }
+
 struct EnvArgs {
   int E, N, C, D, F, S, state_stride, seg, reset, cnt_words;
   uint32_t flags;  // bit 0: non-temporal (streaming) stores for the obs/state flush
@@ -364,6 +388,9 @@ __device__ __forceinline__ void flush_bf16(uint16_t* __restrict__ dst, const flo
 //   WAVE  : 33-64 agents, the env is the whole wave (wave_geometry): scalar env index, addresses, channel
 //           counts and acks, Philox with the wave-uniform head (philox_head_of), the record's ack words built
 //           once per wave.  The step with uint8 masks; same results bit for bit.
+//   REC   : kRecOnly / kRecTables, the record-only wave step (see kCombRecMode).  kRecTables: the LDS is the
+//           table image (comb_table_words), staged by waves 0 and 1 of the workgroup behind its one barrier;
+//           an idle wave of a ragged last workgroup stages its share and retires behind that barrier.
 // LDS: [cnt_words][per-wave obs slots: 64*F floats each][state]
 //   N <= 64 : state staged per wave (the wave's envs), flushed by the wave;
 //   N  > 64 : state of the block's single env staged per block.
@@ -372,12 +399,26 @@ __device__ __forceinline__ void flush_bf16(uint16_t* __restrict__ dst, const flo
 // (bidx = blockIdx.x); the fused env + policy slot (comb_policy_fused_kernel) runs it for the consecutive
 // env groups of its slice and passes lrec, an LDS image of the slice's records (agent k's row of env e at
 // lrec[k * lstride + 2 (e - lenv0)], two 16-byte words) that the slot's policy then reads instead of HBM.
-template <typename MaskT, int DW, bool LARGE, int CT, bool RESET, bool PACKED = false, bool WAVE = false>
+template <typename MaskT, int DW, bool LARGE, int CT, bool RESET, bool PACKED = false, bool WAVE = false, int REC = kRecOff>
 __device__ __forceinline__ void comb_step(const EnvArgs a, float* lds, int bidx, uint4* lrec, int lstride, int lenv0) {
   static_assert(!WAVE || (!LARGE && !RESET && sizeof(MaskT) == 1), "the wave-per-env path: uint8 masks, N <= 64, the step");
+  static_assert(REC == kRecOff || WAVE, "the record-only step is a wave-per-env step");
+  constexpr bool TAB = REC == kRecTables;
+  // REC: the outputs and replay inputs that comb_record_only() found null are null at compile time
+  float* const o_obs = REC ? nullptr : a.obs;
+  float* const o_state = REC ? nullptr : a.state;
+  uint16_t* const o_state_b = REC ? nullptr : a.state_b;
+  void* const o_ack = REC ? nullptr : a.ack;
+  uint8_t* const o_success = REC ? nullptr : a.success;
+  const void* const r_flips = REC ? nullptr : a.flips;
+  const uint8_t* const r_arrivals = REC ? nullptr : a.arrivals;
+  if constexpr (REC) lrec = nullptr;
   const Lane L = WAVE ? wave_geometry(a, bidx) : lane_geometry<LARGE>(a, bidx);
-  if constexpr (WAVE) {
-    if (L.env >= a.E) return;  // an idle wave of a ragged last block (no workgroup barrier follows)
+  // an idle wave of a ragged last block: it retires here where no workgroup barrier follows; TAB, it stages
+  // its share of the table image and retires behind the block's barrier
+  const bool live = !WAVE || L.env < a.E;
+  if constexpr (WAVE && !TAB) {
+    if (!live) return;
   }
   const int N = a.N, F = a.F;
   const int C = CT ? CT : a.C;
@@ -412,23 +453,71 @@ __device__ __forceinline__ void comb_step(const EnvArgs a, float* lds, int bidx,
   philox_head ph{};
   u32x4 flip_r[kWaveFlipBlocks] = {};
   uint32_t arr_r = 0;
-  const bool wave_draws = WAVE && !a.arrivals && (a.draw[0] & (N >= kWave ? ~0ull : ((1ull << N) - 1ull))) != 0;
+  const bool wave_draws = WAVE && !r_arrivals && (a.draw[0] & (N >= kWave ? ~0ull : ((1ull << N) - 1ull))) != 0;
   auto wave_philox = [&]() {
-    if (a.flips && !wave_draws) return;
+    if (r_flips && !wave_draws) return;
     ph = philox_head_of((uint32_t)genv, (uint32_t)L.k, rng_of(a), a.seed);
-    if (!a.flips) {
+    if (!r_flips) {
 #pragma unroll
       for (int blk = 0; blk < kWaveFlipBlocks; ++blk)
         if (blk * 4 < C) flip_r[blk] = philox_tail(ph, (kStreamFlip << 24) | (uint32_t)blk, a.seed);
     }
     if (wave_draws) arr_r = philox_tail(ph, kStreamArrival << 24, a.seed).x;
   };
-  if (L.active) {
-    ag = a.agents[L.k];
+  // TAB: the table image.  Two shares, each staged by one wave of the block for agents k < N: the agent entries
+  // and Poisson heads (wave 0), the flip thresholds of c < C (wave 1).  Their loads are issued here, ahead of the
+  // state loads, and written to LDS right after them: the loads retire in issue order, so the write waits for
+  // the (cached) tables with the state loads still in flight, not for HBM.
+  uint32_t* const img = reinterpret_cast<uint32_t*>(lds);
+  const bool stage_agents = TAB && L.active && L.local_env == 0;
+  const bool stage_thr = TAB && L.active && L.local_env == (L.envs_per_block > 1 ? 1 : 0);
+  uint32_t t_misc = 0;
+  uint64_t t_arr = 0, t_thr[4 * kWaveFlipBlocks] = {};
+  uint4 t_cdf{};
+  if constexpr (TAB) {
+    if (stage_agents) {
+      const d2d_agent_entry* e = a.agents + L.k;
+      t_misc = *reinterpret_cast<const uint32_t*>(e);  // deadline, obs_width, arrival_kind, reserved
+      t_arr = e->arrival_thr;
+      t_cdf = *reinterpret_cast<const uint4*>(a.pois_cdf + (uint32_t)(L.k * 256));
+    }
+    if (stage_thr) {
+      const uint64_t* thr = a.flip_thr + (uint32_t)(L.k * C);
+#pragma unroll
+      for (int c = 0; c < 4 * kWaveFlipBlocks; ++c)
+        if (c < C) t_thr[c] = thr[c];
+    }
+  }
+  auto narrow = [](uint64_t t) { return (t >> 32) ? 0xFFFFFFFFu : (uint32_t)t; };
+  auto stage_store = [&]() {
+    if (stage_agents) {
+      img[kTabMisc + L.k] = t_misc & 0xFFFFFFu;
+      reinterpret_cast<uint4*>(img + kTabArr)[L.k] =
+          ((t_misc >> 16) & 0xFFu) == D2D_ARRIVAL_POISSON ? t_cdf : make_uint4(narrow(t_arr), (t_arr >> 32) ? 1u : 0u, 0u, 0u);
+    }
+    if (stage_thr) {
+      uint32_t always = 0;
+#pragma unroll
+      for (int blk = 0; blk < kWaveFlipBlocks; ++blk) {
+        if (blk * 4 < C) {
+          reinterpret_cast<uint4*>(img + kTabThr)[blk * kWave + L.k] =
+              make_uint4(narrow(t_thr[4 * blk]), narrow(t_thr[4 * blk + 1]), narrow(t_thr[4 * blk + 2]), narrow(t_thr[4 * blk + 3]));
+#pragma unroll
+          for (int i = 0; i < 4; ++i) always |= (uint32_t)((t_thr[4 * blk + i] >> 32) != 0) << (4 * blk + i);
+        }
+      }
+      img[kTabAlways + L.k] = always;
+    }
+  };
+  uint32_t cw_raw = 0;
+  if (L.active && live) {
+    if constexpr (!TAB) ag = a.agents[L.k];
     if (!RESET) {
       load_row<DW>(b, at(a.buf, DW));
       act = (uint32_t)*at(reinterpret_cast<const MaskT*>(a.actions), 1) & cmask;
-      if constexpr (PACKED) {
+      if constexpr (PACKED && TAB) {
+        cw_raw = *at(a.recv, 1);  // unpacked behind the barrier, so that no wave waits for its state ahead of it
+      } else if constexpr (PACKED) {
         // the mask out of the top bytes of the last word; those bytes are zero in the register row, as
         // row_any, the record's word-level build, row_byte and the state output expect
         h_pre = (b.w[DW - 1] >> kMaskShift) & cmask;
@@ -442,9 +531,33 @@ __device__ __forceinline__ void comb_step(const EnvArgs a, float* lds, int bidx,
         dc = *at(a.disc, 1);
       }
     }
+    if constexpr (TAB) stage_store();
     // right after the loads are issued, ahead of their first use (the channel counts): kernel 54.8 -> 54.1 us
     // at 64 x 8 x 65,536 against drawing where the flips are applied
     if constexpr (WAVE) wave_philox();
+  } else if constexpr (TAB) {
+    stage_store();
+  }
+  if constexpr (TAB) {
+    // the block's one barrier: every wave reaches it, the idle waves of a ragged last block too.  LDS writes
+    // alone are awaited (lgkmcnt), the state loads stay in flight across it
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    if (!live) return;
+    if constexpr (PACKED) {  // (an inactive lane's row, mask and counters are zero, and nothing of its is stored)
+      h_pre = (b.w[DW - 1] >> kMaskShift) & cmask;
+      b.w[DW - 1] &= kRowKeep;
+      rc = cw_raw & 0xFFFFu;
+      dc = cw_raw >> 16;
+    }
+    if (L.active) {
+      const uint32_t m = img[kTabMisc + L.k];
+      ag.deadline = (uint8_t)m;
+      ag.obs_width = (uint8_t)(m >> 8);
+      ag.arrival_kind = (uint8_t)(m >> 16);
+    }
   }
   if (LARGE) {
     if (threadIdx.x < 80) cnt[threadIdx.x] = 0;
@@ -500,8 +613,18 @@ __device__ __forceinline__ void comb_step(const EnvArgs a, float* lds, int bidx,
     // evolve_channel: channel_state = |channel_state - Bernoulli(channel_switch)| (116-118, 175)
     uint32_t f = 0;
     if (L.active) {
-      if (a.flips) {
-        f = (uint32_t)*at(reinterpret_cast<const MaskT*>(a.flips), 1);
+      if (r_flips) {
+        f = (uint32_t)*at(reinterpret_cast<const MaskT*>(r_flips), 1);
+      } else if constexpr (TAB) {
+        f = img[kTabAlways + L.k];
+#pragma unroll
+        for (int blk = 0; blk < kWaveFlipBlocks; ++blk) {
+          if (blk * 4 < C) {  // (thresholds of c >= C are staged as 0: no flip)
+            const uint4 t = reinterpret_cast<const uint4*>(img + kTabThr)[blk * kWave + L.k];
+            f |= ((uint32_t)(flip_r[blk].x < t.x) | (uint32_t)(flip_r[blk].y < t.y) << 1 |
+                  (uint32_t)(flip_r[blk].z < t.z) << 2 | (uint32_t)(flip_r[blk].w < t.w) << 3) << (4 * blk);
+          }
+        }
       } else if constexpr (WAVE) {
         const uint64_t* thr = a.flip_thr + (uint32_t)(L.k * C);
 #pragma unroll
@@ -536,8 +659,16 @@ __device__ __forceinline__ void comb_step(const EnvArgs a, float* lds, int bidx,
   const bool drew = L.active && (LARGE ? draws_now(a, L.k) : ((a.draw[0] >> L.k) & 1ull));
   if (drew) {
     uint32_t x;
-    if constexpr (WAVE) {  // arrival_value() on the wave's Philox word
-      if (a.arrivals) x = *at(a.arrivals, 1);
+    if constexpr (TAB) {  // the same from the image; past the staged head of a Poisson row, the global table
+      const uint4 q = reinterpret_cast<const uint4*>(img + kTabArr)[L.k];
+      if (ag.arrival_kind == D2D_ARRIVAL_POISSON) {
+        x = (uint32_t)(arr_r > q.x) + (uint32_t)(arr_r > q.y) + (uint32_t)(arr_r > q.z) + (uint32_t)(arr_r > q.w);
+        if (x == 4u) x = poisson_lookup(arr_r, a.pois_cdf + (uint32_t)(L.k * 256), 4u);
+      } else {
+        x = (uint32_t)(arr_r < q.x) | q.y;
+      }
+    } else if constexpr (WAVE) {  // arrival_value() on the wave's Philox word
+      if (r_arrivals) x = *at(r_arrivals, 1);
       else if (ag.arrival_kind == D2D_ARRIVAL_POISSON) x = poisson_lookup(arr_r, a.pois_cdf + (uint32_t)(L.k * 256));
       else x = (uint64_t)arr_r < ag.arrival_thr ? 1u : 0u;
     } else {
@@ -563,11 +694,11 @@ __device__ __forceinline__ void comb_step(const EnvArgs a, float* lds, int bidx,
       *at(a.disc, 1) = dc;
     }
     if (!RESET) {
-      if (a.success) *at(a.success, 1) = succ ? 1 : 0;
+      if (o_success) *at(o_success, 1) = succ ? 1 : 0;
       if (L.k == 0) {
         if (a.reward) a.reward[L.env] = nsucc;  // rewards = len(successful_users) (211)
-        if (a.ack) {
-          int8_t* ak = reinterpret_cast<int8_t*>(a.ack) + (size_t)L.env * C;
+        if (o_ack) {
+          int8_t* ak = reinterpret_cast<int8_t*>(o_ack) + (size_t)L.env * C;
           for (int c = 0; c < C; ++c) ak[c] = ((ack_one >> c) & 1) ? 1 : (((ack_zero >> c) & 1) ? 0 : -1);
         }
       }
@@ -577,7 +708,7 @@ __device__ __forceinline__ void comb_step(const EnvArgs a, float* lds, int bidx,
   // ---- obs_k = [B'[k,:w_k], channel_obs[k] (pre-evolve), acknack] (199-206)
   const int wave_env0 = LARGE ? bidx : (bidx * L.envs_per_block + wave * epw);
   const int wave_nenv = LARGE ? 1 : max(0, min(epw, a.E - wave_env0));
-  if (a.obs) {
+  if (o_obs) {
     if (L.active) {
       const int lrow = LARGE ? (L.k - wave * kWave) : ((L.local_env - wave * epw) * N + L.k);
       float* o = lds_obs + lrow * F;
@@ -601,9 +732,9 @@ __device__ __forceinline__ void comb_step(const EnvArgs a, float* lds, int bidx,
     if (LARGE) {
       const int k0 = wave * kWave;
       const int nrows = max(0, min(kWave, N - k0));
-      if (nrows > 0) wave_flush(a.obs + ((size_t)bidx * N + k0) * F, lds_obs, nrows * F, a.flags & 1u);
+      if (nrows > 0) wave_flush(o_obs + ((size_t)bidx * N + k0) * F, lds_obs, nrows * F, a.flags & 1u);
     } else if (wave_nenv > 0) {
-      wave_flush(a.obs + (size_t)wave_env0 * N * F, lds_obs, wave_nenv * N * F, a.flags & 1u);
+      wave_flush(o_obs + (size_t)wave_env0 * N * F, lds_obs, wave_nenv * N * F, a.flags & 1u);
     }
   }
   // ---- the same row as the compact record: one byte per obs column (packet counts and channel
@@ -741,7 +872,7 @@ __device__ __forceinline__ void comb_step(const EnvArgs a, float* lds, int bidx,
     }
   }
   // state = [concat_k B'[k,:d_k], channel_state (post-evolve).flatten(), acknack] (207-209)
-  if (a.state || a.state_b) {
+  if (o_state || o_state_b) {
     if (L.active) {
       float* st = lds_state + (LARGE ? 0 : (L.local_env - wave * epw) * a.S);
       const int off = ag.state_offset, d = ag.deadline;
@@ -756,25 +887,26 @@ __device__ __forceinline__ void comb_step(const EnvArgs a, float* lds, int bidx,
     }
     if (LARGE) {
       __syncthreads();
-      if (a.state) flush_rows(a.state + (size_t)bidx * a.state_stride, a.state_stride, lds_state, 1, a.S, a.flags & 1u);
-      if (a.state_b) flush_bf16(a.state_b + (size_t)bidx * a.state_b_ld, lds_state, a.S, threadIdx.x, blockDim.x, a.flags & 1u);
+      if (o_state) flush_rows(o_state + (size_t)bidx * a.state_stride, a.state_stride, lds_state, 1, a.S, a.flags & 1u);
+      if (o_state_b) flush_bf16(o_state_b + (size_t)bidx * a.state_b_ld, lds_state, a.S, threadIdx.x, blockDim.x, a.flags & 1u);
     } else {
       wave_lds_sync();
       for (int r = 0; r < wave_nenv; ++r) {
-        if (a.state)
-          wave_flush(a.state + (size_t)(wave_env0 + r) * a.state_stride, lds_state + r * a.S, a.S, a.flags & 1u);
-        if (a.state_b)
-          flush_bf16(a.state_b + (size_t)(wave_env0 + r) * a.state_b_ld, lds_state + r * a.S, a.S, L.lane, kWave,
+        if (o_state)
+          wave_flush(o_state + (size_t)(wave_env0 + r) * a.state_stride, lds_state + r * a.S, a.S, a.flags & 1u);
+        if (o_state_b)
+          flush_bf16(o_state_b + (size_t)(wave_env0 + r) * a.state_b_ld, lds_state + r * a.S, a.S, L.lane, kWave,
                      a.flags & 1u);
       }
     }
   }
 }
 
-template <typename MaskT, int DW, bool LARGE, int CT, bool RESET, bool PACKED = false, bool WAVE = false>
-__global__ __launch_bounds__(kMaxAgents) __attribute__((amdgpu_waves_per_eu(kCombWavesPerEu))) void comb_kernel(EnvArgs a) {
+template <typename MaskT, int DW, bool LARGE, int CT, bool RESET, bool PACKED = false, bool WAVE = false, int REC = kRecOff>
+__global__ __launch_bounds__(kMaxAgents) __attribute__((amdgpu_waves_per_eu(REC == kRecTables ? kCombTabWavesPerEu : kCombWavesPerEu)))
+void comb_kernel(EnvArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  comb_step<MaskT, DW, LARGE, CT, RESET, PACKED, WAVE>(a, lds, blockIdx.x, nullptr, 0, 0);
+  comb_step<MaskT, DW, LARGE, CT, RESET, PACKED, WAVE, REC>(a, lds, blockIdx.x, nullptr, 0, 0);
 }
 
 // =====================================================================
@@ -1315,11 +1447,20 @@ int set_lds(K kernel, size_t bytes) {
   return D2D_OK;
 }
 
+// The record-only step of the combinatorial env (a.seg set): one env per wave, uint8 masks, a step that writes
+// the record and the reward at most and replays nothing.  dispatch_comb_ct gives it the kCombRecMode
+// instantiation; every other call keeps the plain kernels.
+bool comb_record_only(const EnvArgs& a) {
+  return kCombRecMode != kRecOff && a.N <= kWave && a.seg == kWave && a.C <= 8 && !a.reset && !a.obs && !a.state &&
+         !a.state_b && !a.ack && !a.success && !a.flips && !a.arrivals;
+}
+
 // dynamic LDS of one workgroup (must match the carve in the kernels)
 size_t lds_need(const EnvArgs& a, int block, int kind) {
   const bool large = a.N > kWave;
   const bool stage = a.obs || a.state || a.state_b;
   const bool comb = kind == D2D_ENV_COMBINATORIAL;
+  if (comb && kCombRecMode == kRecTables && comb_record_only(a)) return sizeof(uint32_t) * comb_table_words(a.C);
   if (kind == D2D_ENV_SINGLE) {
     const int epb = large ? 1 : block / a.seg;
     return sizeof(float) * ((size_t)a.cnt_words + (size_t)epb * a.N * (a.D <= 4 ? 2 : a.D <= 8 ? 3 : a.D <= 12 ? 4 : a.D <= 16 ? 5 : 9) +
@@ -1359,6 +1500,10 @@ int dispatch_comb_ct(const EnvArgs& a, int block, hipStream_t s) {
   // uint8 masks only (every CT, packed or not): resets and the uint16 / uint32 masks of C > 8 stay on the
   // segment path, as does the fused slot
   if constexpr (!RESET && sizeof(MaskT) == 1) {
+    if constexpr (kCombRecMode != kRecOff) {
+      if (comb_record_only(a))
+        return launch(comb_kernel<MaskT, DW, false, CT, RESET, PACKED, true, kCombRecMode>, a, block, s, D2D_ENV_COMBINATORIAL);
+    }
     if (a.seg == kWave) return launch(comb_kernel<MaskT, DW, false, CT, RESET, PACKED, true>, a, block, s, D2D_ENV_COMBINATORIAL);
   }
   return launch(comb_kernel<MaskT, DW, false, CT, RESET, PACKED>, a, block, s, D2D_ENV_COMBINATORIAL);
@@ -1479,12 +1624,8 @@ int env_args(const d2d_env_desc* d, const d2d_env_state* st, const d2d_env_packe
   return D2D_OK;
 }
 
-int run_env(const d2d_env_desc* d, const d2d_env_state* st, const d2d_env_packed_state* pst, bool packed,
-            const void* actions, const d2d_env_replay* rp, const d2d_env_out* out, int reset, int t, uint32_t rng_step,
-            void* stream) {
-  EnvArgs a;
-  if (const int rc = env_args(d, st, pst, packed, actions, rp, out, reset, t, rng_step, a)) return rc;
-  const int kind = d->env_kind;
+// the launch geometry of one reset / step: sets a.seg and a.cnt_words, returns the workgroup's lanes
+int env_geometry(EnvArgs& a, int kind) {
   const bool comb = kind == D2D_ENV_COMBINATORIAL;
   const bool large = a.N > kWave;
   int seg = 1;
@@ -1499,12 +1640,23 @@ int run_env(const d2d_env_desc* d, const d2d_env_state* st, const d2d_env_packed
   // 512: 125 us, 1024: 134 us per 65,536 x 64-agent step)
   // 512-lane blocks (8 envs of 64 agents): comb 64 x 8 x 65,536 141 -> 137 us against 256-lane
   // blocks; single: 8 envs per gather-table read (256: 130 us, 512: 125 us, 1024: 134 us)
-  int block = large ? a.seg : (comb && !a.obs && !a.state && !a.state_b) ? kCombRecBlock : 512;
+  int block = large ? a.seg : (comb && comb_record_only(a)) ? kCombTabBlock
+              : (comb && !a.obs && !a.state && !a.state_b) ? kCombRecBlock : 512;
   a.cnt_words = cnt_words(large ? 1 : block / a.seg);
   while (!large && block > kWave && block > a.seg && lds_need(a, block, kind) > 65536) {
     block >>= 1;
     a.cnt_words = cnt_words(block / a.seg);
   }
+  return block;
+}
+
+int run_env(const d2d_env_desc* d, const d2d_env_state* st, const d2d_env_packed_state* pst, bool packed,
+            const void* actions, const d2d_env_replay* rp, const d2d_env_out* out, int reset, int t, uint32_t rng_step,
+            void* stream) {
+  EnvArgs a;
+  if (const int rc = env_args(d, st, pst, packed, actions, rp, out, reset, t, rng_step, a)) return rc;
+  const int kind = d->env_kind;
+  const int block = env_geometry(a, kind);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   switch (buffer_words(a.D)) {
     case 1: return dispatch_dw<1>(a, block, kind, s, packed);
@@ -1639,6 +1791,18 @@ extern "C" int d2d_env_step_packed(const d2d_env_desc* desc, const d2d_env_packe
                                    const d2d_env_replay* replay, const d2d_env_out* out, int32_t timestep,
                                    uint32_t rng_step, void* stream) {
   return run_env(desc, nullptr, st, true, actions, replay, out, 0, timestep, rng_step, stream);
+}
+
+extern "C" int64_t d2d_env_step_lds_bytes(const d2d_env_desc* desc, const d2d_env_replay* replay, const d2d_env_out* out,
+                                          int32_t packed) {
+  // the step's own argument checks and geometry on placeholder state and action pointers (never dereferenced)
+  uint32_t* const p = reinterpret_cast<uint32_t*>(uintptr_t{16});
+  const d2d_env_state st{p, p, p, p, p, p};
+  const d2d_env_packed_state pst{p, p};
+  EnvArgs a;
+  if (const int rc = env_args(desc, &st, &pst, packed != 0, p, replay, out, 0, 1, 0, a)) return rc;
+  const int block = env_geometry(a, desc->env_kind);
+  return (int64_t)lds_need(a, block, desc->env_kind);
 }
 
 namespace {

@@ -119,6 +119,8 @@ _SIGS = {
     "d2d_env_step_packed": (ctypes.c_int, [ctypes.POINTER(EnvDesc), ctypes.POINTER(EnvPackedState), _p,
                                             ctypes.POINTER(EnvReplay), ctypes.POINTER(EnvOut), ctypes.c_int32,
                                             ctypes.c_uint32, _p]),
+    "d2d_env_step_lds_bytes": (ctypes.c_int64, [ctypes.POINTER(EnvDesc), ctypes.POINTER(EnvReplay),
+                                                ctypes.POINTER(EnvOut), ctypes.c_int32]),
     "d2d_env_state_pack": (ctypes.c_int, [ctypes.POINTER(EnvDesc), ctypes.POINTER(EnvState),
                                            ctypes.POINTER(EnvPackedState), _p]),
     "d2d_env_state_unpack": (ctypes.c_int, [ctypes.POINTER(EnvDesc), ctypes.POINTER(EnvPackedState),

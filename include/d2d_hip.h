@@ -55,7 +55,8 @@ extern "C" {
                               still 15, additive: d2d_rdqn_q, d2d_rdqn_grad, d2d_rdqn_grad_workspace (iRDQN);
                               still 15, additive: d2d_env_packed_state, d2d_env_reset_packed, d2d_env_step_packed,
                               d2d_env_state_pack, d2d_env_state_unpack (no layout change);
-                              still 15, additive: d2d_rdqn_q_ex, d2d_rdqn_grad_ex, d2d_rdqn_carry_floats */
+                              still 15, additive: d2d_rdqn_q_ex, d2d_rdqn_grad_ex, d2d_rdqn_carry_floats;
+                              still 15, additive: d2d_env_step_lds_bytes (host-only query) */
 
 enum { D2D_ENV_COMBINATORIAL = 0, D2D_ENV_CHANNEL_SELECTION = 1, D2D_ENV_SINGLE = 2 };
 enum { D2D_ARRIVAL_POISSON = 0, D2D_ARRIVAL_SCHEDULED_BERNOULLI = 1, D2D_ARRIVAL_NONE = 2 };
@@ -105,7 +106,8 @@ typedef struct d2d_env_desc {
      * exp(-lam), p = p * lam / x, F += p (x <= 254), t[k][255] = 2^32 - 1; the draw of word r is the
      * number of leading entries with r > t[k][x] -- bitwise the sequential inversion of the reference
      * oracle (oracle/philox.py poisson_inversion), without a double division per step.  Rows of
-     * non-Poisson agents are never read.  Required (spec.py poisson_cdf_table builds it). */
+     * non-Poisson agents are never used (the record-only step loads the first 16 bytes of every row k < N
+     * and drops them).  Required (spec.py poisson_cdf_table builds it). */
     const uint32_t* poisson_cdf;
 } d2d_env_desc;
 
@@ -193,6 +195,14 @@ int d2d_env_reset_packed(const d2d_env_desc* desc, const d2d_env_packed_state* s
 int d2d_env_step_packed(const d2d_env_desc* desc, const d2d_env_packed_state* st, const void* actions,
                         const d2d_env_replay* replay, const d2d_env_out* out, int32_t timestep, uint32_t rng_step,
                         void* stream);
+
+/* Host-only (no HIP call): the dynamic LDS bytes per workgroup of the kernel that d2d_env_step (packed = 0) or
+ * d2d_env_step_packed (packed != 0) would launch for this desc, replay and out; a negative D2D_E* where the step
+ * would refuse the arguments.  The record-only step of the combinatorial env with 33-64 agents and C <= 8 (no
+ * obs, state, state_bf16, ack or success output, no replay) stages the per-agent tables in LDS once per
+ * workgroup: 1536 + 1024 * ceil(C / 4) bytes. */
+int64_t d2d_env_step_lds_bytes(const d2d_env_desc* desc, const d2d_env_replay* replay, const d2d_env_out* out,
+                               int32_t packed);
 
 /* Elementwise conversions, one lane per agent row (sel_quality / sel_count are not used): unpacked -> packed
  * (counters truncated to 16 bits: see the bound) and packed -> unpacked.  For reading the state as the public
