@@ -198,6 +198,15 @@ class BatchedLearnerBase(DataParallelMixin):
                                and os.environ.get("D2D_FUSED_UPDATE", "1") != "0")
         return self._fused_upd
 
+    # opt-in (fused_optimizer=True / D2D_FUSED_OPTIM=1): the parameter update -- the per-agent gradient-norm clip and
+    # Adam -- as one d2d_adam_step call (d2dhip.optim.StackedAdam) instead of torch's foreach Adam.  It rounds
+    # differently from torch's, so the default stays torch.optim.Adam
+    fused_optimizer = os.environ.get("D2D_FUSED_OPTIM", "0") == "1"
+
+    def _stacked_adam(self, params, n_agents, lr, eps=1e-8, max_norm=None):
+        from d2dhip.optim import StackedAdam
+        return StackedAdam(list(params), n_agents, lr=lr, eps=eps, max_norm=max_norm)
+
     @staticmethod
     def _grad_buffers(params):
         """The .grad tensors of agent-stacked params (allocated once; the kernels overwrite them)."""

@@ -104,8 +104,10 @@ class D2DPPO(BatchedLearnerBase):
                  save_path=None,
                  combinatorial=False,
                  history_len=10,
-                 early_stopping=True):
+                 early_stopping=True, *, fused_optimizer=None):
         self.env = env
+        if fused_optimizer is not None:
+            self.fused_optimizer = bool(fused_optimizer)
         self.history_len = history_len
         self.n_agents = env.n_agents
         self.hidden_size = hidden_size
@@ -135,11 +137,17 @@ class D2DPPO(BatchedLearnerBase):
         # The value network is at the BS (d2d_ppo.py:264-267)
         self.value_network = Value(self.env.state_space.shape[0], hidden_size)
         self.value_network = self.value_network.to(self.device)
-        self.value_optimizer = torch.optim.Adam(self.value_network.parameters(), lr=value_lr)
+        if self.fused_optimizer:  # one net, one global norm: clip_grad_norm_(value_network.parameters(), 20)
+            self.value_optimizer = self._stacked_adam(self.value_network.parameters(), 1, value_lr, max_norm=20)
+        else:
+            self.value_optimizer = torch.optim.Adam(self.value_network.parameters(), lr=value_lr)
         in_dims = [env.observation_space[k].shape[0] for k in range(self.n_agents)]
         self.policy = StackedNets([a.policy_network for a in self.agents], in_dims,
                                   "rnn" if useRNN else "mlp", self.device, act=self._policy_act())
-        self.policy_optimizer = torch.optim.Adam(self.policy.parameters(), lr=policy_lr)
+        if self.fused_optimizer:  # grad_norm_clip_(20) per agent + Adam in one call
+            self.policy_optimizer = self._stacked_adam(self.policy.parameters(), self.n_agents, policy_lr, max_norm=20)
+        else:
+            self.policy_optimizer = torch.optim.Adam(self.policy.parameters(), lr=policy_lr)
         self._setup_data_parallel(self.policy.parameters() + list(self.value_network.parameters()))
 
     # ------------------------------------------------------------ rollouts
@@ -210,14 +218,16 @@ class D2DPPO(BatchedLearnerBase):
         self.policy_optimizer.zero_grad()
         ploss.sum().backward()
         self._reduce_grads(self.policy.parameters())
-        self.policy.grad_norm_clip_(20)
+        if not self.fused_optimizer:  # (StackedAdam clips per agent at 20 itself)
+            self.policy.grad_norm_clip_(20)
         self.policy_optimizer.step()
         # 4) critic update (d2d_ppo.py:440-446)
         value_loss = F.mse_loss(values, ro.ret_mean, reduction='mean')
         self.value_optimizer.zero_grad()
         value_loss.backward()
         self._reduce_grads(list(self.value_network.parameters()))
-        torch.nn.utils.clip_grad_norm_(self.value_network.parameters(), 20)
+        if not self.fused_optimizer:
+            torch.nn.utils.clip_grad_norm_(self.value_network.parameters(), 20)
         self.value_optimizer.step()
         pl = ploss.detach().cpu().numpy()
         return [float(pl[i]) for i in cycle], value_loss.detach()
@@ -265,7 +275,8 @@ class D2DPPO(BatchedLearnerBase):
         self._phase("actor_grad")
         self._reduce_grads(self.policy.parameters())
         self._phase("allreduce")
-        self.policy.grad_norm_clip_(20)
+        if not self.fused_optimizer:  # (StackedAdam clips per agent at 20 itself)
+            self.policy.grad_norm_clip_(20)
         self.policy_optimizer.step()
         self._phase("adam")
         ploss = -(sa[:, 0] + beta * sa[:, 1]) / (T * E)
@@ -278,7 +289,8 @@ class D2DPPO(BatchedLearnerBase):
         self._phase("critic_grad")
         self._reduce_grads(list(self.value_network.parameters()))
         self._phase("allreduce")
-        torch.nn.utils.clip_grad_norm_(self.value_network.parameters(), 20)
+        if not self.fused_optimizer:
+            torch.nn.utils.clip_grad_norm_(self.value_network.parameters(), 20)
         self.value_optimizer.step()
         self._phase("adam")
         pl = ploss.detach().cpu().numpy()

@@ -129,8 +129,10 @@ class iPPO(BatchedLearnerBase):
                  save_path=None,
                  combinatorial=False,
                  history_len=10,
-                 early_stopping=True):
+                 early_stopping=True, *, fused_optimizer=None):
         self.env = env
+        if fused_optimizer is not None:
+            self.fused_optimizer = bool(fused_optimizer)
         self.history_len = history_len
         self.n_agents = env.n_agents
         self.hidden_size = hidden_size
@@ -161,8 +163,12 @@ class iPPO(BatchedLearnerBase):
         self.policy = StackedNets([a.policy_network for a in self.agents], in_dims, kind, self.device,
                                   act=self._policy_act())
         self.value = StackedNets([a.value_network for a in self.agents], in_dims, kind, self.device, act=None)
-        self.policy_optimizer = torch.optim.Adam(self.policy.parameters(), lr=policy_lr)
-        self.value_optimizer = torch.optim.Adam(self.value.parameters(), lr=value_lr)
+        if self.fused_optimizer:  # no clipping in iPPO (ippo.py:204-215)
+            self.policy_optimizer = self._stacked_adam(self.policy.parameters(), self.n_agents, policy_lr)
+            self.value_optimizer = self._stacked_adam(self.value.parameters(), self.n_agents, value_lr)
+        else:
+            self.policy_optimizer = torch.optim.Adam(self.policy.parameters(), lr=policy_lr)
+            self.value_optimizer = torch.optim.Adam(self.value.parameters(), lr=value_lr)
         self._setup_data_parallel(self.policy.parameters() + self.value.parameters())
 
     # ------------------------------------------------------------ rollouts
@@ -242,7 +248,8 @@ class iPPO(BatchedLearnerBase):
 
     def _epoch_fused(self, ro, cliprange=0.1, beta=0.01):
         """The same epoch on the fused HIP update kernels: gradients of every agent's policy loss
-        and value loss straight from the rollout buffers, written into .grad; Adam in torch."""
+        and value loss straight from the rollout buffers, written into .grad; Adam in torch, or one d2d_adam_step
+        call per optimizer with fused_optimizer=True."""
         from d2dhip.update import actor_grads, critic_grads
         pp, vp = self.policy.params, self.value.params
         kind = "comb" if self.combinatorial else "chsel"

@@ -21,6 +21,7 @@ Reference semantics kept (each exactly the reference's at n_envs = 1): see episo
 DESIGN.md §4.9.  Not implemented: a callable `loss` (NotImplementedError); shapes outside the kernels' envelope
 (hidden <= 128, obs + 1 <= 64, n_channels <= 16, history_len <= 256) raise NotImplementedError.
 """
+import functools
 import math
 import os
 import random
@@ -243,16 +244,33 @@ class DQN:
         return self.network(state).argmax().item()
 
 
+def _fused_optimizer_kwarg(init):
+    """iRDQN(..., fused_optimizer=True / False) without another named parameter: the constructor's signature -- the
+    reference's order, then replay_record -- is pinned (tests/test_irdqn_record_cpu.py), so the keyword is taken
+    off here, before the constructor proper runs, and overrides the class default (D2D_FUSED_OPTIM)."""
+    @functools.wraps(init)
+    def wrapped(self, *args, fused_optimizer=None, **kw):
+        if fused_optimizer is not None:
+            self.fused_optimizer = bool(fused_optimizer)
+        return init(self, *args, **kw)
+    return wrapped
+
+
 class iRDQN(BatchedLearnerBase):
     # the replay / test rings as the compact obs record instead of fp32 rows (the same results, a quarter of the bytes)
     replay_record = os.environ.get("D2D_RDQN_RECORD", "0") == "1"
     # acting slots carry their hidden state while the window is an episode prefix (the same results, fewer GRU steps)
     carry_state = os.environ.get("D2D_RDQN_CARRY", "1") != "0"
 
+    @_fused_optimizer_kwarg
     def __init__(self, env, history_len=5, replay_start_size=50000, replay_buffer_size=1000000, gamma=0.99,
                  update_target_frequency=10000, minibatch_size=32, learning_rate=1e-3, update_frequency=1,
                  initial_exploration_rate=1, final_exploration_rate=0.1, adam_epsilon=1e-8, loss='huber',
                  early_stopping=True, *, replay_record=None):
+        """The reference's arguments, then two keyword-only switches: replay_record (the replay ring as the compact obs
+        record) and fused_optimizer (True: the Adam step as one d2d_adam_step call, d2dhip.optim.StackedAdam; None: the
+        class default, D2D_FUSED_OPTIM).  fused_optimizer is accepted by the _fused_optimizer_kwarg wrapper and does
+        not show in this signature or in help()."""
         self.device = self._resolve_device(None)
         if self.device.type != "cuda":
             import d2dhip
@@ -295,7 +313,11 @@ class iRDQN(BatchedLearnerBase):
         if self.network.A != env.n_channels:
             raise NotImplementedError("iRDQN needs one action per channel")
         rdqn.check_envelope(self.network.F, self.network.H, self.network.A, history_len)
-        self.optimizer = torch.optim.Adam(self.network.parameters(), lr=learning_rate, eps=adam_epsilon)
+        if self.fused_optimizer:
+            self.optimizer = self._stacked_adam(self.network.parameters(), self.n_agents, learning_rate,
+                                                eps=adam_epsilon)
+        else:
+            self.optimizer = torch.optim.Adam(self.network.parameters(), lr=learning_rate, eps=adam_epsilon)
         self.losses = []          # per update: loss [N] (device tensors)
         self.n_updates = self.n_syncs = 0
 

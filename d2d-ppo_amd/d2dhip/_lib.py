@@ -104,6 +104,21 @@ class RdqnDesc(ctypes.Structure):
                 ("w3", _p), ("b3", _p), ("seed", ctypes.c_uint64), ("env_base", ctypes.c_uint64), ("rng_offset", _p)]
 
 
+D2D_ADAM_MAX_TENSORS = 16
+
+
+class AdamTensor(ctypes.Structure):
+    """d2d_adam_tensor: agent k's slice is [k * numel, (k + 1) * numel) of each pointer."""
+    _fields_ = [("param", _p), ("grad", _p), ("exp_avg", _p), ("exp_avg_sq", _p), ("numel", ctypes.c_int64)]
+
+
+class AdamDesc(ctypes.Structure):
+    _fields_ = [("n_agents", ctypes.c_int32), ("n_tensors", ctypes.c_int32),
+                ("tensors", AdamTensor * D2D_ADAM_MAX_TENSORS),
+                ("lr", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double),
+                ("eps", ctypes.c_double), ("max_norm", ctypes.c_double), ("step", ctypes.c_int64), ("step_dev", _p)]
+
+
 D2D_RDQN_GREEDY, D2D_RDQN_EPS, D2D_RDQN_FORCED = 0, 1, 2
 D2D_RDQN_HUBER, D2D_RDQN_MSE = 0, 1
 
@@ -214,6 +229,8 @@ _SIGS = {
     "d2d_rdqn_grad_ex": (ctypes.c_int, [ctypes.POINTER(RdqnDesc), _p, ctypes.c_int32, _p, _p, ctypes.c_int32,
                                          ctypes.c_int32, _p, _p, _p, _p, ctypes.c_float, ctypes.c_int32] + [_p] * 12
                          + [ctypes.c_int64, _p]),
+    "d2d_adam_workspace": (ctypes.c_int64, [ctypes.POINTER(AdamDesc)]),
+    "d2d_adam_step": (ctypes.c_int, [ctypes.POINTER(AdamDesc), _p, ctypes.c_int64, _p, _p]),
     "d2d_last_error": (ctypes.c_char_p, []),
     "d2d_abi_version": (ctypes.c_int, []),
 }

@@ -56,7 +56,8 @@ extern "C" {
                               still 15, additive: d2d_env_packed_state, d2d_env_reset_packed, d2d_env_step_packed,
                               d2d_env_state_pack, d2d_env_state_unpack (no layout change);
                               still 15, additive: d2d_rdqn_q_ex, d2d_rdqn_grad_ex, d2d_rdqn_carry_floats;
-                              still 15, additive: d2d_env_step_lds_bytes (host-only query) */
+                              still 15, additive: d2d_env_step_lds_bytes (host-only query);
+                              still 15, additive: d2d_adam_step, d2d_adam_workspace (the optimizer) */
 
 enum { D2D_ENV_COMBINATORIAL = 0, D2D_ENV_CHANNEL_SELECTION = 1, D2D_ENV_SINGLE = 2 };
 enum { D2D_ARRIVAL_POISSON = 0, D2D_ARRIVAL_SCHEDULED_BERNOULLI = 1, D2D_ARRIVAL_NONE = 2 };
@@ -671,6 +672,44 @@ int d2d_rdqn_grad_ex(const d2d_rdqn_desc* desc, const void* obs, int32_t obs_for
                      const uint8_t* done, const float* qmax_target, float gamma, int32_t loss_kind, float* g_w_ih,
                      float* g_w_hh, float* g_b_ih, float* g_b_hh, float* g_w1, float* g_b1, float* g_w2, float* g_b2,
                      float* g_w3, float* g_b3, float* loss, float* workspace, int64_t workspace_floats, void* stream);
+
+/* The parameter update (additive, ABI 15; csrc/optim_kernels.hip): torch.nn.utils.clip_grad_norm_ per agent followed
+ * by torch.optim.Adam at its defaults (no amsgrad, no weight decay), element-wise in fp32 -- ippo.py:204-215,
+ * d2d_ppo.py:209-212 and 443-446, irdqn.py:144-146 of the reference.  Every tensor is agent-stacked: agent k's slice
+ * is [k * numel, (k + 1) * numel) of each pointer; pointers are 4-byte aligned (16-byte accesses are used where the
+ * four pointers of a tensor share their address modulo 16, at any slice alignment).
+ *   max_norm > 0: norm_k = sqrt(sum g^2) over all tensors of agent k, coef_k = min(1, max_norm / (norm_k + 1e-6));
+ *     g <- coef_k g is written back (.grad holds the clipped gradient, as after clip_grad_norm_) and
+ *     grad_norm[k] = norm_k, the value before clipping (grad_norm is not written without clipping).  A zero gradient
+ *     gives coef = 1.
+ *   m <- m + (g - m)(1 - beta1); v <- beta2 v + (1 - beta2) g g; bc2s = sqrt(1 - beta2^t) and
+ *     step_size = lr / (1 - beta1^t) in double, rounded to float once; p <- p - step_size (m / (sqrt(v) / bc2s + eps)).
+ *   step_dev (device int64, optional): incremented first, then used as t, so replays of a captured graph advance it;
+ *     else t = step >= 1.
+ * The norm is summed in a fixed order that depends on the sizes alone, without atomics: equal inputs give equal bits.
+ * The call never allocates: the table travels in the kernel arguments, the workspace (d2d_adam_workspace bytes,
+ * 8-byte aligned; 0 without clipping) holds the norm partials.  Launches: 1 without clipping on a host step, 2 with
+ * step_dev, 3 with clipping.  n_agents = 0 or all numel = 0: D2D_OK, nothing launched (step_dev does not advance).
+ * D2D_EINVAL (before any HIP call): NULL desc; n_tensors outside [1, 16]; a negative n_agents or numel; a NULL or
+ * misaligned pointer of a non-empty tensor; step < 1 without step_dev; beta1 or beta2 outside [0, 1); eps < 0; lr < 0;
+ * a workspace that is NULL, too small or not 8-byte aligned when one is needed.  D2D_EUNSUPPORTED: clipping with
+ * n_agents > 65535.  d2d_adam_workspace returns the bytes, or -1 for a desc d2d_adam_step would refuse.  A NaN or
+ * infinite norm behaves as in torch: coef is NaN (0 for an infinite norm) and goes into that agent's gradient. */
+#define D2D_ADAM_MAX_TENSORS 16            /* the iRDQN Q-net has 10, the GRU nets 8, the MLPs 4 */
+typedef struct d2d_adam_tensor {
+    float *param, *grad, *exp_avg, *exp_avg_sq;
+    int64_t numel;                         /* per agent */
+} d2d_adam_tensor;
+typedef struct d2d_adam_desc {
+    int32_t n_agents, n_tensors;           /* n_agents = 1: one net, one global norm (the D2D central critic) */
+    d2d_adam_tensor tensors[D2D_ADAM_MAX_TENSORS];
+    double lr, beta1, beta2, eps;
+    double max_norm;                       /* <= 0: no clipping */
+    int64_t step;                          /* t >= 1 of this step, used when step_dev == NULL */
+    int64_t* step_dev;                     /* device counter: incremented first, then used */
+} d2d_adam_desc;
+int64_t d2d_adam_workspace(const d2d_adam_desc* desc);
+int d2d_adam_step(const d2d_adam_desc* desc, void* workspace, int64_t workspace_bytes, float* grad_norm, void* stream);
 
 /* Process-wide tuning options (not part of the reference interface).
  * D2D_OPT_NT_STORES: 1 = write obs/state with non-temporal (streaming) stores.  Default: 0.
